@@ -11,6 +11,10 @@ global_batch * (src_len + tgt_len): every counted token is embedded and
 processed by the full encoder or decoder stack each step.
 
 Rank 0 prints exactly ONE JSON line with the result.
+
+A plain run does only what that figure needs: setup, warmup, the timed
+steps, the optional --dump-outputs write, the result line.  Anything
+further belongs behind --full.
 """
 
 from __future__ import annotations
@@ -31,6 +35,33 @@ MODELS = {
 }
 
 
+DUMP_MAX_ELEMS = 4 * 1024 * 1024  # per array: 16 MB fp32, 3 arrays < 64 MB
+
+
+def dump_outputs(out_dir, loss, opt):
+    """Write what the last timed step computed as <out_dir>/<name>.npy
+    (float32): the loss it returned, and the flat gradient and fp32 master
+    weight buffers it left behind.  Buffers larger than DUMP_MAX_ELEMS are
+    written as a fixed seeded sample (same indices for every run of the
+    same model), so two builds can be compared element for element."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, t):
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator(device="cpu").manual_seed(97531)
+            idx = torch.randint(0, t.numel(), (DUMP_MAX_ELEMS,), generator=g)
+            t = t[idx.sort().values.to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"),
+                t.float().cpu().numpy())
+
+    save("loss", loss)
+    save("grads", opt.flat.flat_g)
+    save("master_weights", opt.master)
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
@@ -46,7 +77,17 @@ def main():
     p.add_argument("--graph", action="store_true",
                    help="capture the step into a hipGraph and replay "
                         "(single-GPU only)")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed "
+                        "step computed (loss, gradients, fp32 master "
+                        "weights) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements beyond the headline "
+                        "figure (none at present: the plain run already "
+                        "does only setup, warmup and the timed steps)")
     args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
 
     from transformer_amd.models import Transformer
     from transformer_amd.parallel import init_distributed, BucketedDataParallel
@@ -145,6 +186,9 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, opt)
 
     ms_per_step = elapsed / args.steps * 1000.0
     tokens_per_step = global_batch * (S + S)

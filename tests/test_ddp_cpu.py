@@ -278,7 +278,11 @@ def test_distributed_train_entry_point_subprocess(tmp_path, toy_corpus):
          "--epochs", "1", "--num_layers", "1", "--d_model", "32",
          "--dff", "64", "--num_heads", "2", "--batch_size", "8",
          "--sequence_length", "40", "--noenable_function"],
-        capture_output=True, text=True, timeout=540)
+        capture_output=True, text=True, timeout=540,
+        # RCCL rejects two ranks on one device: keep both ranks on CPU
+        # (gloo) even on a box that has a GPU
+        env={**os.environ, "HIP_VISIBLE_DEVICES": "-1",
+             "CUDA_VISIBLE_DEVICES": "-1"})
     assert out.returncode == 0, (out.stderr[-3000:], out.stdout[-1000:])
     assert os.path.isdir(tmp_path / "ckpt"), "no rank-0 checkpoint directory"
 

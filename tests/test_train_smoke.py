@@ -118,8 +118,10 @@ def test_train_entry_point_subprocess(tmp_path, toy_corpus):
          "--src_vocab_file", str(tmp_path / "sv"),
          "--tgt_vocab_file", str(tmp_path / "tv"),
          "--ckpt_path", str(tmp_path / "ckpt"),
-         "--epochs", "1", "--num_layers", "1", "--d_model", "32",
-         "--dff", "64", "--num_heads", "2", "--batch_size", "8",
+         # head dim 32: the smallest the HIP attention kernel accepts, so
+         # the same command runs on a GPU box as on a CPU-only one
+         "--epochs", "1", "--num_layers", "1", "--d_model", "64",
+         "--dff", "128", "--num_heads", "2", "--batch_size", "8",
          "--sequence_length", "40", "--noenable_function",
          "--steps_per_epoch", "3"],
         capture_output=True, text=True, timeout=600,
