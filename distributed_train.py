@@ -35,7 +35,8 @@ def main(epochs, enable_function, buffer_size, batch_size, sequence_length,
          warmup_steps=60000, label_smoothing=0.0, device=None, dtype=None,
          seed=1234, log_interval=100, eval_steps=50, synthetic_data=False,
          synthetic_vocab=32768, steps_per_epoch=100, max_decode_len=10,
-         debug_sync=False, **_ignored):
+         debug_sync=False, clip_grad_norm=0.0, skip_nonfinite_grads=False,
+         **_ignored):
     if debug_sync:  # race/fault localization mode
         os.environ["AMD_SERIALIZE_KERNEL"] = "3"
         os.environ["HIP_LAUNCH_BLOCKING"] = "1"
@@ -86,7 +87,9 @@ def main(epochs, enable_function, buffer_size, batch_size, sequence_length,
         train_log_dir, test_log_dir, max_ckpt_keep, ckpt_path, d_model,
         warmup_steps=warmup_steps, label_smoothing=label_smoothing,
         device=device, log_interval=log_interval, eval_steps=eval_steps,
-        max_decode_len=max_decode_len, is_rank0=(rank == 0))
+        max_decode_len=max_decode_len, is_rank0=(rank == 0),
+        clip_grad_norm=clip_grad_norm,
+        skip_nonfinite_grads=skip_nonfinite_grads)
     train.load_ckpt()
     train.training_loop(train_ds, test_ds)
     if rank == 0:

@@ -58,7 +58,8 @@ def main(epochs, enable_function, buffer_size, batch_size, sequence_length,
          warmup_steps=60000, label_smoothing=0.0, device=None, dtype=None,
          seed=1234, log_interval=100, eval_steps=50, synthetic_data=False,
          synthetic_vocab=32768, steps_per_epoch=100, max_decode_len=10,
-         trace_dir=None, debug_sync=False, **_ignored):
+         trace_dir=None, debug_sync=False, clip_grad_norm=0.0,
+         skip_nonfinite_grads=False, **_ignored):
     if debug_sync:
         # race/fault localization: every kernel launch is
         # serialized and synchronous so a fault is attributed to the
@@ -99,7 +100,9 @@ def main(epochs, enable_function, buffer_size, batch_size, sequence_length,
                   ckpt_path, d_model, warmup_steps=warmup_steps,
                   label_smoothing=label_smoothing, device=device,
                   log_interval=log_interval, eval_steps=eval_steps,
-                  max_decode_len=max_decode_len)
+                  max_decode_len=max_decode_len,
+                  clip_grad_norm=clip_grad_norm,
+                  skip_nonfinite_grads=skip_nonfinite_grads)
     train.load_ckpt()
     train.install_signal_handler()  # SIGTERM/SIGINT -> checkpoint + exit
     if trace_dir:

@@ -94,6 +94,10 @@ def transformer_flags(parser: argparse.ArgumentParser | None = None) -> argparse
                              " — race/fault localization mode, SURVEY.md §5")
     parser.add_argument("--max_decode_len", type=int, default=10,
                         help="greedy decode steps for predict (reference train.py:109 uses 10)")
+    parser.add_argument("--clip_grad_norm", type=float, default=0.0,
+                        help="clip gradients to this global L2 norm; 0 = off")
+    _add_bool_flag(parser, "skip_nonfinite_grads", False,
+                   "skip optimizer steps whose gradient norm is not finite")
     return parser
 
 
@@ -130,6 +134,8 @@ def flags_dict(args: argparse.Namespace) -> dict:
         "steps_per_epoch": args.steps_per_epoch,
         "max_decode_len": args.max_decode_len,
         "debug_sync": args.debug_sync,
+        "clip_grad_norm": args.clip_grad_norm,
+        "skip_nonfinite_grads": args.skip_nonfinite_grads,
     }
 
 

@@ -112,6 +112,92 @@ __global__ void adam_dev_kernel(float* __restrict__ master,
   }
 }
 
+// ---- clipped / skippable variants -----------------------------------------
+// `stats` = {norm, scale, skipped_this_step, skipped_total}, written by
+// grad_norm_clip (grad_clip.hip) earlier on the same stream.  The gradient is
+// multiplied by stats[1] in fp32 before the m/v updates; when stats[2] != 0
+// the kernel returns before any store (NOT a multiply by zero: 0*inf = NaN).
+//
+// Both clipped kernels share the one body below.  adam_kernel and
+// adam_dev_kernel above keep their own text on purpose: routing them through
+// a shared inline function made hipcc pick a different mul+add contraction
+// for the m update, i.e. different last bits from what they produced before.
+// The shared body therefore spells the fused multiply-adds out, in the form
+// the vector path of adam_kernel compiles to, so that with scale == 1 a
+// clipped update of a 4-aligned buffer is bit-identical to the unclipped one
+// whatever the compiler would have chosen here.
+DEV_INLINE float adam_elem(float g, float& mj, float& vj, float w, float lr,
+                           float b1, float b2, float eps, float bc1,
+                           float bc2) {
+  mj = __builtin_fmaf(1.f - b1, g, b1 * mj);
+  vj = __builtin_fmaf(b2, vj, (1.f - b2) * g * g);
+  return w - lr * (mj * bc1) / (sqrtf(vj * bc2) + eps);
+}
+
+DEV_INLINE void adam_clip_update(float* __restrict__ master,
+                                 float* __restrict__ m, float* __restrict__ v,
+                                 const short* __restrict__ grad,
+                                 short* __restrict__ param, long n, float lr,
+                                 float b1, float b2, float eps, float bc1,
+                                 float bc2, float gscale) {
+  long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (i + 4 <= n) {
+    f32x4 mm = *(const f32x4*)(m + i);
+    f32x4 vv = *(const f32x4*)(v + i);
+    f32x4 ww = *(const f32x4*)(master + i);
+    s16x4 g4 = *(const s16x4*)(grad + i);
+    s16x4 p4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float mj = mm[j], vj = vv[j];
+      float w = adam_elem(bfbits2f(g4[j]) * gscale, mj, vj, ww[j], lr, b1, b2,
+                          eps, bc1, bc2);
+      mm[j] = mj;
+      vv[j] = vj;
+      ww[j] = w;
+      p4[j] = f2bfbits(w);
+    }
+    *(f32x4*)(m + i) = mm;
+    *(f32x4*)(v + i) = vv;
+    *(f32x4*)(master + i) = ww;
+    *(s16x4*)(param + i) = p4;
+  } else {
+    for (long j = i; j < n; ++j) {
+      float mj = m[j], vj = v[j];
+      float w = adam_elem(bfbits2f(grad[j]) * gscale, mj, vj, master[j], lr,
+                          b1, b2, eps, bc1, bc2);
+      m[j] = mj;
+      v[j] = vj;
+      master[j] = w;
+      param[j] = f2bfbits(w);
+    }
+  }
+}
+
+__global__ void adam_clip_kernel(float* __restrict__ master,
+                                 float* __restrict__ m, float* __restrict__ v,
+                                 const short* __restrict__ grad,
+                                 short* __restrict__ param, long n, float lr,
+                                 float b1, float b2, float eps, float bc1,
+                                 float bc2, const float* __restrict__ stats) {
+  if (stats[2] != 0.f) return;
+  adam_clip_update(master, m, v, grad, param, n, lr, b1, b2, eps, bc1, bc2,
+                   stats[1]);
+}
+
+__global__ void adam_dev_clip_kernel(float* __restrict__ master,
+                                     float* __restrict__ m,
+                                     float* __restrict__ v,
+                                     const short* __restrict__ grad,
+                                     short* __restrict__ param, long n,
+                                     const float* __restrict__ coefs, float b1,
+                                     float b2, float eps,
+                                     const float* __restrict__ stats) {
+  if (stats[2] != 0.f) return;
+  adam_clip_update(master, m, v, grad, param, n, coefs[0], b1, b2, eps,
+                   coefs[1], coefs[2], stats[1]);
+}
+
 // Graph-capturable fused Adam: advances `step` (int64[1], device) and runs
 // the update with the device-derived Noam lr.  d_model/warmup fixed.
 void adam_fused_dev(torch::Tensor master, torch::Tensor m, torch::Tensor v,
@@ -150,4 +236,72 @@ void adam_fused(torch::Tensor master, torch::Tensor m, torch::Tensor v,
       master.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
       (const short*)grad.data_ptr(), (short*)param.data_ptr(), n, (float)lr,
       (float)beta1, (float)beta2, (float)eps, bc1, bc2);
+}
+
+static void check_clip_args(const torch::Tensor& master,
+                            const torch::Tensor& m, const torch::Tensor& v,
+                            const torch::Tensor& grad,
+                            const torch::Tensor& param,
+                            const torch::Tensor& stats) {
+  TORCH_CHECK(master.is_cuda() && master.dtype() == torch::kFloat32 &&
+              master.is_contiguous());
+  TORCH_CHECK(m.is_cuda() && m.dtype() == torch::kFloat32 &&
+              m.is_contiguous() && v.is_cuda() &&
+              v.dtype() == torch::kFloat32 && v.is_contiguous());
+  TORCH_CHECK(grad.is_cuda() && grad.dtype() == torch::kBFloat16 &&
+              grad.is_contiguous() && param.is_cuda() &&
+              param.dtype() == torch::kBFloat16 && param.is_contiguous());
+  const long n = master.numel();
+  TORCH_CHECK(m.numel() == n && v.numel() == n && grad.numel() == n &&
+              param.numel() == n);
+  TORCH_CHECK(stats.is_cuda() && stats.dtype() == torch::kFloat32 &&
+              stats.is_contiguous() && stats.numel() >= 4);
+  TORCH_CHECK(stats.get_device() == master.get_device() &&
+              grad.get_device() == master.get_device());
+}
+
+// adam_fused with the gradient scaled by stats[1] (fp32, before the m/v
+// updates) and the whole update vetoed when stats[2] != 0.  `stats` is the
+// buffer written by grad_norm_clip on the same stream.
+void adam_fused_clip(torch::Tensor master, torch::Tensor m, torch::Tensor v,
+                     torch::Tensor grad, torch::Tensor param, double lr,
+                     double beta1, double beta2, double eps, int64_t step,
+                     torch::Tensor stats) {
+  check_clip_args(master, m, v, grad, param, stats);
+  long n = master.numel();
+  float bc1 = 1.0f / (1.0f - powf((float)beta1, (float)step));
+  float bc2 = 1.0f / (1.0f - powf((float)beta2, (float)step));
+  auto stream = at::hip::getCurrentHIPStream();
+  adam_clip_kernel<<<((n + 3) / 4 + 255) / 256, 256, 0, stream>>>(
+      master.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
+      (const short*)grad.data_ptr(), (short*)param.data_ptr(), n, (float)lr,
+      (float)beta1, (float)beta2, (float)eps, bc1, bc2,
+      stats.data_ptr<float>());
+}
+
+// Graph-capturable clipped Adam.  The device step tensor advances even on a
+// skipped step, so the Noam schedule and the host step counter stay in
+// lock-step with no sync.
+void adam_fused_dev_clip(torch::Tensor master, torch::Tensor m,
+                         torch::Tensor v, torch::Tensor grad,
+                         torch::Tensor param, torch::Tensor step,
+                         torch::Tensor coefs, double d_model, double warmup,
+                         double beta1, double beta2, double eps,
+                         torch::Tensor stats) {
+  check_clip_args(master, m, v, grad, param, stats);
+  TORCH_CHECK(step.dtype() == torch::kInt64 && step.numel() == 1 &&
+              step.is_cuda());
+  TORCH_CHECK(coefs.dtype() == torch::kFloat32 && coefs.numel() >= 3 &&
+              coefs.is_cuda());
+  long n = master.numel();
+  auto stream = at::hip::getCurrentHIPStream();
+  adam_coefs_kernel<<<1, 1, 0, stream>>>(
+      (long long*)step.data_ptr(), coefs.data_ptr<float>(),
+      1.0f / sqrtf((float)d_model),
+      powf((float)warmup, -1.5f), (float)beta1, (float)beta2);
+  adam_dev_clip_kernel<<<((n + 3) / 4 + 255) / 256, 256, 0, stream>>>(
+      master.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
+      (const short*)grad.data_ptr(), (short*)param.data_ptr(), n,
+      coefs.data_ptr<float>(), (float)beta1, (float)beta2, (float)eps,
+      stats.data_ptr<float>());
 }

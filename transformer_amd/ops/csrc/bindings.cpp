@@ -89,6 +89,21 @@ void adam_fused_dev(torch::Tensor master, torch::Tensor m, torch::Tensor v,
 void adam_fused(torch::Tensor master, torch::Tensor m, torch::Tensor v,
                 torch::Tensor grad, torch::Tensor param, double lr,
                 double beta1, double beta2, double eps, int64_t step);
+void adam_fused_clip(torch::Tensor master, torch::Tensor m, torch::Tensor v,
+                     torch::Tensor grad, torch::Tensor param, double lr,
+                     double beta1, double beta2, double eps, int64_t step,
+                     torch::Tensor stats);
+void adam_fused_dev_clip(torch::Tensor master, torch::Tensor m,
+                         torch::Tensor v, torch::Tensor grad,
+                         torch::Tensor param, torch::Tensor step,
+                         torch::Tensor coefs, double d_model, double warmup,
+                         double beta1, double beta2, double eps,
+                         torch::Tensor stats);
+void grad_norm_clip(torch::Tensor grad, torch::Tensor partials,
+                    torch::Tensor stats, double max_norm,
+                    bool skip_nonfinite);
+int64_t grad_norm_blocks(int64_t n);
+int64_t grad_norm_max_blocks();
 
 torch::Tensor argmax_lastdim(torch::Tensor logits);
 std::vector<int64_t> accuracy(torch::Tensor logits, torch::Tensor targets);
@@ -180,6 +195,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adam_fused", &adam_fused);
   m.def("adam_fused_dev", &adam_fused_dev,
         "graph-capturable Adam: device step tensor + in-kernel Noam lr");
+  m.def("adam_fused_clip", &adam_fused_clip,
+        "adam_fused with grad*stats[1]; no store at all when stats[2] != 0");
+  m.def("adam_fused_dev_clip", &adam_fused_dev_clip,
+        "adam_fused_dev with grad*stats[1]; a skipped step (stats[2] != 0) "
+        "still advances the device step tensor");
+  m.def("grad_norm_clip", &grad_norm_clip,
+        "deterministic two-stage L2 norm of a 1-D bf16 tensor; stats = "
+        "{norm, scale, skipped_this_step, skipped_total}",
+        pybind11::arg("grad"), pybind11::arg("partials"),
+        pybind11::arg("stats"), pybind11::arg("max_norm"),
+        pybind11::arg("skip_nonfinite"));
+  m.def("grad_norm_blocks", &grad_norm_blocks,
+        "stage-1 block count (= workspace elements) for a length-n input");
+  m.def("grad_norm_max_blocks", &grad_norm_max_blocks);
   m.def("argmax_lastdim", &argmax_lastdim);
   m.def("accuracy", &accuracy);
 }

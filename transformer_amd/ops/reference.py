@@ -160,3 +160,22 @@ def adam_step_reference(param, grad, m, v, step: int, lr: float,
     vhat = v / (1 - beta2 ** step)
     param.sub_(lr * mhat / (vhat.sqrt() + eps))
     return param
+
+
+def global_grad_norm_reference(grads) -> float:
+    """L2 norm over a list of gradient tensors, accumulated in fp64 (the
+    oracle for the two-stage HIP reduction grad_norm_clip).  Returns inf/nan
+    when any element is non-finite."""
+    total = 0.0
+    for g in grads:
+        total += float(g.detach().double().pow(2).sum())
+    return math.sqrt(total) if total == total else float("nan")
+
+
+def clip_scale_reference(norm: float, max_norm: float) -> float:
+    """Gradient scale of the global-norm clip: exactly 1.0 when clipping is
+    off (max_norm <= 0) or the norm is within bounds, else
+    max_norm / (norm + 1e-6)."""
+    if max_norm <= 0 or norm <= max_norm:
+        return 1.0
+    return max_norm / (norm + 1e-6)

@@ -10,9 +10,19 @@ slices (parallel/ddp.py) — fewer, larger collectives for xGMI.
 
 CPU path: per-parameter fp32 Adam via ops/reference.py (the kernel's
 numerics oracle).
+
+Optional guard (off by default): global-norm gradient clipping and skipping
+of non-finite steps.  On the GPU flat path the norm, the clip scale and the
+skip decision are computed and consumed ON DEVICE (grad_clip.hip + the
+clipped Adam kernels), so a hipGraph-captured step can veto itself without
+a host sync.  flat_g's alignment padding is always zero, so one reduction
+over the buffer is the exact global norm; it is also the buffer the DP
+runtime all-reduces, so every rank takes the same decision.
 """
 
 from __future__ import annotations
+
+import math
 
 import torch
 
@@ -20,6 +30,7 @@ from ..ops import ext, has_ext, reference as R
 from .schedule import NoamSchedule
 
 _ALIGN = 64  # elements; keeps every param slice 128-byte aligned for kernels
+_F32_MAX = 3.4028234663852886e38
 
 
 class FlatParams:
@@ -87,14 +98,31 @@ class NoamAdam:
     """Adam with the Noam schedule computed host-side per step (K15).
 
     GPU: one fused HIP kernel over the whole flat parameter set.
-    CPU: reference per-tensor fp32 Adam."""
+    CPU: reference per-tensor fp32 Adam.
+
+    max_grad_norm > 0 clips the gradient to that global L2 norm
+    (scale = max_norm / (norm + 1e-6) when norm > max_norm, else exactly 1).
+    skip_nonfinite=True drops a step whose fp32 sum of squared gradients is
+    not finite — inf/NaN elements, and also a finite but absurd gradient
+    whose sum of squares overflows fp32 (norm > ~1.8e19): master, m, v and
+    the weights stay untouched, `skipped_steps` grows by one, and
+    `step_count` (hence the Noam schedule) still advances.  With both off
+    (the default) step()/step_captured() launch exactly the unguarded
+    kernels."""
 
     def __init__(self, model: torch.nn.Module, d_model: int,
                  warmup_steps: int = 60000, betas=(0.9, 0.98), eps: float = 1e-9,
-                 use_flat: bool | None = None):
+                 use_flat: bool | None = None, max_grad_norm: float = 0.0,
+                 skip_nonfinite: bool = False):
         self.schedule = NoamSchedule(d_model, warmup_steps)
         self.betas, self.eps = betas, eps
         self.step_count = 0
+        self.max_grad_norm = float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.guarded = self.max_grad_norm > 0 or self.skip_nonfinite
+        self._skipped = 0       # host count (CPU paths / restored value)
+        self._last_norm = 0.0   # host value (CPU paths)
+        self._gn_stats = None   # device {norm, scale, skipped, skipped_total}
         p0 = next(model.parameters())
         self.is_cuda = p0.is_cuda
         if use_flat is None:
@@ -113,6 +141,46 @@ class NoamAdam:
                  "master": p.detach().float().clone()}
                 for p in self.params
             ]
+        if self.guarded and self.flat is not None and self.is_cuda:
+            # allocated once, never inside a capture
+            dev = self.flat.flat_g.device
+            self._gn_ws = torch.empty(
+                ext().grad_norm_blocks(self.flat.numel), dtype=torch.float32,
+                device=dev)
+            self._gn_stats = torch.zeros(4, dtype=torch.float32, device=dev)
+
+    # ---- gradient guard ---------------------------------------------------
+    def last_grad_norm(self) -> float:
+        """Global gradient norm (pre-clip) of the most recent guarded step.
+        On the GPU this reads the device stats buffer and therefore
+        SYNCHRONISES — call it at logging cadence, not per step."""
+        if self._gn_stats is not None:
+            return float(self._gn_stats[0].item())
+        return self._last_norm
+
+    @property
+    def skipped_steps(self) -> int:
+        """Steps dropped as non-finite so far.  The GPU count lives on the
+        device (it is advanced inside captured graphs), so reading it
+        synchronises."""
+        if self._gn_stats is not None:
+            return int(self._gn_stats[3].item())
+        return self._skipped
+
+    def _device_norm_pass(self):
+        ext().grad_norm_clip(self.flat.flat_g, self._gn_ws, self._gn_stats,
+                             self.max_grad_norm, self.skip_nonfinite)
+
+    def _host_guard(self, grads):
+        """CPU semantics of the device guard: (skip, scale)."""
+        norm = R.global_grad_norm_reference(grads)
+        self._last_norm = norm
+        # same rule as the kernel: the fp32 sum of squares must be finite
+        if self.skip_nonfinite and not (math.isfinite(norm)
+                                        and norm * norm <= _F32_MAX):
+            self._skipped += 1
+            return True, 1.0
+        return False, R.clip_scale_reference(norm, self.max_grad_norm)
 
     @property
     def lr(self) -> float:
@@ -135,11 +203,23 @@ class NoamAdam:
         """Graph-capturable optimizer step: the Noam lr and Adam bias
         corrections are derived ON DEVICE from a step tensor advanced
         in-graph, so a replayed graph keeps the schedule moving.  The host
-        `step_count` must be advanced by the replay wrapper."""
+        `step_count` must be advanced by the replay wrapper.
+
+        With the gradient guard on, the norm pass and the clipped Adam
+        kernel are captured instead.  On a skipped step the device step
+        tensor STILL advances, so the Noam schedule and the host
+        `step_count` stay in lock-step with no sync."""
         from ..ops import ext as _ext_fn
         st, cf = self.graph_state()
         b1, b2 = self.betas
         self.flat.check()
+        if self.guarded:
+            self._device_norm_pass()
+            _ext_fn().adam_fused_dev_clip(
+                self.master, self.m, self.v, self.flat.flat_g,
+                self.flat.flat_w, st, cf, self.schedule.d_model,
+                self.schedule.warmup_steps, b1, b2, self.eps, self._gn_stats)
+            return
         _ext_fn().adam_fused_dev(self.master, self.m, self.v,
                                   self.flat.flat_g, self.flat.flat_w, st, cf,
                                   self.schedule.d_model,
@@ -161,6 +241,8 @@ class NoamAdam:
         self.step_count += 1
         lr = self.schedule(self.step_count)
         b1, b2 = self.betas
+        if self.guarded:
+            return self._guarded_step(lr, b1, b2)
         if self.flat is not None:
             self.flat.check()
             if self.is_cuda:
@@ -181,9 +263,44 @@ class NoamAdam:
                                       self.eps)
                 p.data.copy_(st["master"].to(p.dtype))
 
+    def _guarded_step(self, lr, b1, b2):
+        """step() with clipping and/or non-finite skipping engaged."""
+        if self.flat is not None:
+            self.flat.check()
+            if self.is_cuda:
+                self._device_norm_pass()
+                ext().adam_fused_clip(self.master, self.m, self.v,
+                                      self.flat.flat_g, self.flat.flat_w,
+                                      lr, b1, b2, self.eps, self.step_count,
+                                      self._gn_stats)
+                return
+            skip, scale = self._host_guard([self.flat.flat_g])
+            if skip:
+                return
+            g = self.flat.flat_g.float()
+            if scale != 1.0:
+                g = g * scale
+            R.adam_step_reference(self.master, g, self.m, self.v,
+                                  self.step_count, lr, b1, b2, self.eps)
+            self.flat.flat_w.copy_(self.master.to(self.flat.flat_w.dtype))
+            return
+        live = [(p, st) for p, st in zip(self.params, self.state)
+                if p.grad is not None]
+        skip, scale = self._host_guard([p.grad for p, _ in live])
+        if skip:
+            return
+        for p, st in live:
+            g = p.grad.float()
+            if scale != 1.0:
+                g = g * scale
+            R.adam_step_reference(st["master"], g, st["m"], st["v"],
+                                  self.step_count, lr, b1, b2, self.eps)
+            p.data.copy_(st["master"].to(p.dtype))
+
     # -- checkpointing (C16) ------------------------------------------------
     def state_dict(self):
         d = {"step": self.step_count,
+             "skipped_steps": self.skipped_steps,
              "d_model": self.schedule.d_model,
              "warmup_steps": self.schedule.warmup_steps}
         if self.flat is not None:
@@ -194,6 +311,10 @@ class NoamAdam:
 
     def load_state_dict(self, d):
         self.step_count = d["step"]
+        # absent in checkpoints written before the guard existed
+        self._skipped = int(d.get("skipped_steps", 0))
+        if self._gn_stats is not None:
+            self._gn_stats[3] = float(self._skipped)
         if hasattr(self, "_step_t"):  # keep captured-graph schedule in sync
             self._step_t.fill_(self.step_count)
         if self.flat is not None:

@@ -29,7 +29,9 @@ class Train:
                  warmup_steps: int = 60000, label_smoothing: float = 0.0,
                  device=None, log_interval: int = 100, eval_steps: int = 50,
                  max_decode_len: int = 10, is_rank0: bool = True,
-                 use_flat: bool | None = None):
+                 use_flat: bool | None = None,
+                 clip_grad_norm: float = 0.0,
+                 skip_nonfinite_grads: bool = False):
         self.epochs = epochs
         self.enable_function = enable_function
         self.transformer = transformer
@@ -45,7 +47,9 @@ class Train:
         self.device = device if device is not None else p0.device
 
         self.optimizer = NoamAdam(transformer, d_model, warmup_steps,
-                                  use_flat=use_flat)
+                                  use_flat=use_flat,
+                                  max_grad_norm=clip_grad_norm,
+                                  skip_nonfinite=skip_nonfinite_grads)
         self.train_loss = Mean("train_loss")
         self.test_loss = Mean("test_loss")
         self.train_accuracy = Mean("train_accuracy")
@@ -102,6 +106,8 @@ class Train:
         self.optimizer.zero_grad()
         loss.backward()
         self._grad_sync()
+        # clip/skip (if enabled) acts on the all-reduced flat gradient, so
+        # every rank takes the identical decision with no extra collective
         self.optimizer.step()
 
         self.train_loss.update(loss.detach().item())
@@ -261,6 +267,15 @@ class Train:
                     if self.train_summary_writer:
                         self.train_summary_writer.add_scalar(
                             "tokens_per_sec", tps, step)
+                        if self.optimizer.guarded:
+                            # the only device reads of the guard: once per
+                            # interval, so graph replays stay sync-free
+                            self.train_summary_writer.add_scalar(
+                                "grad_norm",
+                                self.optimizer.last_grad_norm(), step)
+                            self.train_summary_writer.add_scalar(
+                                "skipped_steps",
+                                self.optimizer.skipped_steps, step)
 
             # end-of-epoch eval so the epoch summary always reflects a real
             # test sweep (Q8/Q10: the reference could silently report
