@@ -51,7 +51,11 @@ class SelfAttention(nn.Module):
         self.w_o = nn.Parameter(_glorot(d_model, d_model))
         self.b_o = nn.Parameter(torch.zeros(d_model))
 
-    def forward(self, x, kv_pad=None, causal=False, return_weights=False):
+    def forward(self, x, kv_pad=None, causal=False, return_weights=False,
+                project=True):
+        """project=False returns the merged heads BEFORE the output
+        projection — the layer then runs w_o/b_o fused with its
+        dropout + residual LayerNorm (one autograd node)."""
         B, S, d = x.shape
         qkv = ops.linear(x, self.w_qkv, self.b_qkv)          # (B,S,3d)
         qkv = qkv.view(B, S, 3, self.num_heads, self.depth)
@@ -62,7 +66,8 @@ class SelfAttention(nn.Module):
         if return_weights:
             out, w = out
         out = out.reshape(B, S, d)
-        out = ops.linear(out, self.w_o, self.b_o)
+        if project:
+            out = ops.linear(out, self.w_o, self.b_o)
         return (out, w) if return_weights else (out, None)
 
 
@@ -82,7 +87,8 @@ class CrossAttention(nn.Module):
         self.w_o = nn.Parameter(_glorot(d_model, d_model))
         self.b_o = nn.Parameter(torch.zeros(d_model))
 
-    def forward(self, x, enc_output, kv_pad=None, return_weights=False):
+    def forward(self, x, enc_output, kv_pad=None, return_weights=False,
+                project=True):
         B, Sq, d = x.shape
         Sk = enc_output.shape[1]
         q = ops.linear(x, self.w_q, self.b_q).view(B, Sq, self.num_heads, self.depth)
@@ -93,7 +99,8 @@ class CrossAttention(nn.Module):
         if return_weights:
             out, w = out
         out = out.reshape(B, Sq, d)
-        out = ops.linear(out, self.w_o, self.b_o)
+        if project:
+            out = ops.linear(out, self.w_o, self.b_o)
         return (out, w) if return_weights else (out, None)
 
 
@@ -111,6 +118,20 @@ class FeedForward(nn.Module):
     def forward(self, x):
         h = ops.linear(x, self.w1, self.b1, activation="relu")
         return ops.linear(h, self.w2, self.b2)
+
+
+def _proj_ln(mha, heads, res, ln, rate, training):
+    """LN(dropout(heads @ w_o^T + b_o) + res)."""
+    return ops.linear_dropout_residual_layernorm(
+        heads, mha.w_o, mha.b_o, res, ln.gamma, ln.beta, rate, training,
+        ln.eps)
+
+
+def _ffn_ln(ffn, x, ln, rate, training):
+    """LN(dropout(ffn(x)) + x)."""
+    return ops.ffn_dropout_residual_layernorm(
+        x, ffn.w1, ffn.b1, ffn.w2, ffn.b2, ln.gamma, ln.beta, rate, training,
+        ln.eps)
 
 
 class _LN(nn.Module):
@@ -134,14 +155,9 @@ class EncoderLayer(nn.Module):
         self.rate = rate
 
     def forward(self, x, kv_pad, training):
-        attn, _ = self.mha(x, kv_pad=kv_pad, causal=False)
-        out1 = ops.dropout_residual_layernorm(attn, x, self.ln1.gamma,
-                                              self.ln1.beta, self.rate,
-                                              training, self.ln1.eps)
-        ffn = self.ffn(out1)
-        return ops.dropout_residual_layernorm(ffn, out1, self.ln2.gamma,
-                                              self.ln2.beta, self.rate,
-                                              training, self.ln2.eps)
+        heads, _ = self.mha(x, kv_pad=kv_pad, causal=False, project=False)
+        out1 = _proj_ln(self.mha, heads, x, self.ln1, self.rate, training)
+        return _ffn_ln(self.ffn, out1, self.ln2, self.rate, training)
 
 
 class DecoderLayer(nn.Module):
@@ -160,20 +176,14 @@ class DecoderLayer(nn.Module):
 
     def forward(self, x, enc_output, tgt_pad, src_pad, training,
                 return_weights=False):
-        attn1, w1 = self.mha1(x, kv_pad=tgt_pad, causal=True,
-                              return_weights=return_weights)
-        out1 = ops.dropout_residual_layernorm(attn1, x, self.ln1.gamma,
-                                              self.ln1.beta, self.rate,
-                                              training, self.ln1.eps)
-        attn2, w2 = self.mha2(out1, enc_output, kv_pad=src_pad,
-                              return_weights=return_weights)
-        out2 = ops.dropout_residual_layernorm(attn2, out1, self.ln2.gamma,
-                                               self.ln2.beta, self.rate,
-                                               training, self.ln2.eps)
-        ffn = self.ffn(out2)
-        out3 = ops.dropout_residual_layernorm(ffn, out2, self.ln3.gamma,
-                                               self.ln3.beta, self.rate,
-                                               training, self.ln3.eps)
+        heads1, w1 = self.mha1(x, kv_pad=tgt_pad, causal=True,
+                               return_weights=return_weights, project=False)
+        out1 = _proj_ln(self.mha1, heads1, x, self.ln1, self.rate, training)
+        heads2, w2 = self.mha2(out1, enc_output, kv_pad=src_pad,
+                               return_weights=return_weights, project=False)
+        out2 = _proj_ln(self.mha2, heads2, out1, self.ln2, self.rate,
+                        training)
+        out3 = _ffn_ln(self.ffn, out2, self.ln3, self.rate, training)
         return out3, w1, w2
 
 

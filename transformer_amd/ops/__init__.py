@@ -54,6 +54,8 @@ from .functional import (  # noqa: E402
     cross_attention,
     residual_layernorm,
     dropout_residual_layernorm,
+    linear_dropout_residual_layernorm,
+    ffn_dropout_residual_layernorm,
     embedding_scale_pe,
     embedding_scale_pe_at,
     dropout,

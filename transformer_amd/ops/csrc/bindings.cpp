@@ -9,7 +9,9 @@
 torch::Tensor gemm_nt(torch::Tensor a, torch::Tensor w, torch::Tensor bias,
                       int64_t epilogue, c10::optional<torch::Tensor> out);
 torch::Tensor gemm256_nt(torch::Tensor a, torch::Tensor w, torch::Tensor bias,
-                         int64_t epilogue, c10::optional<torch::Tensor> out);
+                         int64_t epilogue, c10::optional<torch::Tensor> out,
+                         c10::optional<torch::Tensor> aux);
+bool gemm256_viable(int M, int N, int K, int lda, int ldb);
 torch::Tensor gemm128_nt(torch::Tensor a, torch::Tensor w, torch::Tensor bias,
                          int64_t epilogue, c10::optional<torch::Tensor> out);
 torch::Tensor gemm_dw(torch::Tensor dy, torch::Tensor x,
@@ -49,7 +51,8 @@ std::vector<torch::Tensor> ln_bwd(torch::Tensor dy, torch::Tensor s,
                                   c10::optional<torch::Tensor> dgamma_out,
                                   c10::optional<torch::Tensor> dbeta_out,
                                   c10::optional<torch::Tensor> mask,
-                                  double p);
+                                  double p,
+                                  c10::optional<torch::Tensor> dbias_out);
 
 std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k,
                                     torch::Tensor v, torch::Tensor kv_pad,
@@ -124,9 +127,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("a"), pybind11::arg("w"), pybind11::arg("bias"),
         pybind11::arg("epilogue"), pybind11::arg("out") = pybind11::none());
   m.def("gemm256_nt", &gemm256_nt,
-        "256x256 deep-pipelined NT GEMM (K%32==0; M/N any, edge-clamped)",
+        "256x256 deep-pipelined NT GEMM (K%64==0; M/N any, edge-clamped); "
+        "epilogue 0=none 1=relu, with aux (M,N): 2=relu-mask (aux>0 ? c : 0) "
+        "3=residual-add (c + aux, one rounding)",
         pybind11::arg("a"), pybind11::arg("w"), pybind11::arg("bias"),
-        pybind11::arg("epilogue"), pybind11::arg("out") = pybind11::none());
+        pybind11::arg("epilogue"), pybind11::arg("out") = pybind11::none(),
+        pybind11::arg("aux") = pybind11::none());
+  m.def("gemm256_viable",
+        [](int M, int N, int K) { return gemm256_viable(M, N, K, K, K); },
+        "whether gemm_nt dispatches (M,N,K) to the 256-tile kernel");
   m.def("gemm_nn", &gemm_nn, "C[M,N] = A[M,K] @ B[K,N] (dX)",
         pybind11::arg("a"), pybind11::arg("b"),
         pybind11::arg("out") = pybind11::none());
@@ -171,7 +180,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("dgamma_out") = pybind11::none(),
         pybind11::arg("dbeta_out") = pybind11::none(),
         pybind11::arg("mask") = pybind11::none(),
-        pybind11::arg("p") = 0.0);
+        pybind11::arg("p") = 0.0,
+        pybind11::arg("dbias_out") = pybind11::none());
   m.def("attn_fwd", &attn_fwd, pybind11::arg("q"), pybind11::arg("k"),
         pybind11::arg("v"), pybind11::arg("kv_pad"), pybind11::arg("causal"),
         pybind11::arg("scale"), pybind11::arg("trv") = 1);

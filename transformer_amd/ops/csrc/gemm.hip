@@ -585,7 +585,8 @@ torch::Tensor gemm_launch(torch::Tensor a, torch::Tensor b, torch::Tensor bias,
 // Implemented in gemm256.hip: deep-pipelined 256x256 kernel + viability.
 bool gemm256_viable(int M, int N, int K, int lda, int ldb);
 torch::Tensor gemm256_nt(torch::Tensor a, torch::Tensor w, torch::Tensor bias,
-                         int64_t epilogue, c10::optional<torch::Tensor> out);
+                         int64_t epilogue, c10::optional<torch::Tensor> out,
+                         c10::optional<torch::Tensor> aux);
 
 // C[M,N] = A[M,K] @ W[N,K]^T (+bias)(+ReLU) — forward layout.
 torch::Tensor gemm_nt(torch::Tensor a, torch::Tensor w, torch::Tensor bias,
@@ -595,7 +596,7 @@ torch::Tensor gemm_nt(torch::Tensor a, torch::Tensor w, torch::Tensor bias,
   const int M = a.size(0), K = a.size(1), N = w.size(0);
   TORCH_CHECK(w.size(1) == K, "gemm_nt: K mismatch");
   if (gemm256_viable(M, N, K, K, K))
-    return gemm256_nt(a, w, bias, epilogue, out);
+    return gemm256_nt(a, w, bias, epilogue, out, c10::nullopt);
   return gemm_launch<false, false>(a, w, bias, epilogue, M, N, K, K, K, out);
 }
 

@@ -93,7 +93,7 @@ __global__ __launch_bounds__(G_THREADS, 1)
 void gemm256_kernel(const short* __restrict__ A, const short* __restrict__ B,
                     const short* __restrict__ bias, short* __restrict__ C,
                     int M, int N, int K, int lda, int ldb, int has_bias,
-                    int nbm, int nbn) {
+                    int nbm, int nbn, const short* __restrict__ aux) {
   constexpr int MF = BM_ / 32;          // A row-frags per wave (8 or 4)
   constexpr int NF = BN_ / 64;          // B col-frags per wave (4 or 2)
   constexpr int A_ELEMS = BM_ * G_BK;   // shorts per A tile
@@ -215,6 +215,10 @@ void gemm256_kernel(const short* __restrict__ A, const short* __restrict__ B,
   }
 
   // Epilogue: C/D lane map col = lane&15, row = (lane>>4)*4 + r.
+  // EPILOGUE 0 none, 1 bias+ReLU forward; the backward modes read an
+  // (M, N) bf16 aux tensor at the element they store (no bias):
+  //   2 relu-mask    C = aux > 0 ? bf16(acc) : 0   (== relu_bwd(C, aux))
+  //   3 residual-add C = bf16(acc + aux)           (one rounding)
 #pragma unroll
   for (int i = 0; i < MF; ++i) {
     const int grow_base = bm0 + wm + i * 16 + kg * 4;
@@ -229,7 +233,11 @@ void gemm256_kernel(const short* __restrict__ A, const short* __restrict__ B,
         if (grow >= M) continue;
         float v = acc[i][j][r] + bv;
         if (EPILOGUE == 1) v = fmaxf(v, 0.0f);
-        C[(long)grow * N + gcol] = f2bfbits(v);
+        if (EPILOGUE == 3) v += bfbits2f(aux[(long)grow * N + gcol]);
+        short o = f2bfbits(v);
+        if (EPILOGUE == 2)
+          o = bfbits2f(aux[(long)grow * N + gcol]) > 0.f ? o : (short)0;
+        C[(long)grow * N + gcol] = o;
       }
     }
   }
@@ -274,7 +282,8 @@ bool gemm256_viable(int M, int N, int K, int lda, int ldb) {
 }
 
 torch::Tensor gemm256_nt(torch::Tensor a, torch::Tensor w, torch::Tensor bias,
-                         int64_t epilogue, c10::optional<torch::Tensor> out) {
+                         int64_t epilogue, c10::optional<torch::Tensor> out,
+                         c10::optional<torch::Tensor> aux) {
   TORCH_CHECK(a.is_cuda() && a.dtype() == torch::kBFloat16 && a.dim() == 2 &&
               a.is_contiguous(), "gemm256_nt: a must be contiguous bf16 2-D");
   TORCH_CHECK(w.is_cuda() && w.dtype() == torch::kBFloat16 && w.dim() == 2 &&
@@ -283,13 +292,27 @@ torch::Tensor gemm256_nt(torch::Tensor a, torch::Tensor w, torch::Tensor bias,
   TORCH_CHECK(w.size(1) == K, "gemm256_nt: K mismatch");
   TORCH_CHECK(K % G_BK == 0 && K >= 2 * G_BK,
               "gemm256_nt: K must be a multiple of 64 (>=128)");
-  const bool has_bias = bias.defined() && bias.numel() > 0;
+  TORCH_CHECK(epilogue >= 0 && epilogue <= 3, "gemm256_nt: bad epilogue");
+  const bool has_bias = epilogue < 2 && bias.defined() && bias.numel() > 0;
+  const short* auxp = nullptr;
+  if (epilogue >= 2) {
+    TORCH_CHECK(aux.has_value() && aux->is_cuda() &&
+                aux->dtype() == torch::kBFloat16 && aux->dim() == 2 &&
+                aux->is_contiguous() && aux->size(0) == M &&
+                aux->size(1) == N,
+                "gemm256_nt: epilogue 2/3 needs a contiguous bf16 (M, N) aux");
+    TORCH_CHECK(!(bias.defined() && bias.numel() > 0),
+                "gemm256_nt: epilogue 2/3 takes no bias");
+    auxp = (const short*)aux->data_ptr();
+  }
   torch::Tensor c;
   if (out.has_value()) {
     c = *out;
     TORCH_CHECK(c.is_cuda() && c.dtype() == torch::kBFloat16 &&
                 c.is_contiguous() && c.numel() == (long)M * N,
                 "out must be contiguous bf16 with M*N elements");
+    TORCH_CHECK(!auxp || c.data_ptr() != (void*)auxp,
+                "gemm256_nt: out must not alias aux");
   } else {
     c = torch::empty({M, N}, a.options());
   }
@@ -298,7 +321,7 @@ torch::Tensor gemm256_nt(torch::Tensor a, torch::Tensor w, torch::Tensor bias,
   const int nbm = cdiv(M, BMv), nbn = cdiv(N, BNv);
   const size_t smem = 2 * ((size_t)BMv + BNv) * G_BK * sizeof(short);
   auto stream = at::hip::getCurrentHIPStream();
-  static bool attr_set[2][3] = {};
+  static bool attr_set[4][3] = {};  // [epilogue][tile]
   // tile-walk order / XCD-remap variants (TFMX_G256_ORDER=nm,
   // TFMX_G256_XCD=0 for the A/B prober; huge-N shapes pick n-major by
   // the measured rule below)
@@ -330,7 +353,8 @@ torch::Tensor gemm256_nt(torch::Tensor a, torch::Tensor w, torch::Tensor bias,
           <<<nbm * nbn, G_THREADS, smem, stream>>>(
               (const short*)a.data_ptr(), (const short*)w.data_ptr(),
               has_bias ? (const short*)bias.data_ptr() : nullptr,
-              (short*)c.data_ptr(), M, N, K, K, K, has_bias, nbm, nbn);
+              (short*)c.data_ptr(), M, N, K, K, K, has_bias, nbm, nbn,
+              auxp);
     };
     using I0 = std::integral_constant<int, 0>;
     using I1 = std::integral_constant<int, 1>;
@@ -339,6 +363,8 @@ torch::Tensor gemm256_nt(torch::Tensor a, torch::Tensor w, torch::Tensor bias,
   };
   using E0 = std::integral_constant<int, 0>;
   using E1 = std::integral_constant<int, 1>;
+  using E2 = std::integral_constant<int, 2>;
+  using E3 = std::integral_constant<int, 3>;
   using T256 = std::integral_constant<int, 256>;
   using T128 = std::integral_constant<int, 128>;
   auto dis = [&](auto epi) {
@@ -346,6 +372,9 @@ torch::Tensor gemm256_nt(torch::Tensor a, torch::Tensor w, torch::Tensor bias,
     else if (BNv == 128) launch(epi, T256{}, T128{});
     else launch(epi, T256{}, T256{});
   };
-  if (epilogue == 1) dis(E1{}); else dis(E0{});
+  if (epilogue == 3) dis(E3{});
+  else if (epilogue == 2) dis(E2{});
+  else if (epilogue == 1) dis(E1{});
+  else dis(E0{});
   return c;
 }

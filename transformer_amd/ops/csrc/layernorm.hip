@@ -7,6 +7,9 @@
 // workspaces with atomics, then cast to bf16.
 #include "common.h"
 
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
 #include <map>
 
 #include <torch/extension.h>
@@ -267,6 +270,210 @@ void ln_gb_kernel(const short* __restrict__ dy, const short* __restrict__ s,
   }
 }
 
+// One-pass backward: ln_bwd_kernel's per-element math (same lane mapping,
+// c = lane*8 + chunk*512, same summation order -> dx/dxm bit-identical)
+// with the three column sums carried in registers.  A lane's columns are
+// the same for every row it visits, so dgamma/dbeta/dbias accumulate in
+// fp32 registers across a grid-stride row loop; dy and s are read ONCE
+// (ln_bwd + ln_gb + colsum re-read them ~2.7x).  After its rows a block
+// combines its waves through LDS, adds 3*D fp32 atomics (256-B contiguous
+// per wave instruction, start segment rotated by block so the few-hundred
+// co-finishing blocks do not hit the same lines in lockstep) into the
+// cached workspace [dgamma D | dbeta D | dbias D | counter], and the last
+// arriver casts to bf16 and re-zeroes.  (Spreading the blocks over 4-64
+// copies of the accumulator rows measured no faster: docs/PERF.md.)  NCH = 512-column chunks per row
+// (1: D <= 512, 2: D <= 1024); needs D % 8 == 0.  NW = waves per block
+// (a power of two);
+// the host caps the grid at LNF_ROWS_PER_PASS / NW blocks.
+#define LNF_ROWS_PER_PASS 4096
+template <bool DROP, int NCH, int NW>
+__global__ __launch_bounds__(NW * 64)
+void ln_bwd_fused_kernel(const short* __restrict__ dy,
+                         const short* __restrict__ s,
+                         const short* __restrict__ gamma,
+                         const float* __restrict__ mean,
+                         const float* __restrict__ rstd,
+                         short* __restrict__ dx, int R, int D,
+                         const unsigned char* __restrict__ mask,
+                         short* __restrict__ dxm, float inv_keep,
+                         float* __restrict__ ws, short* __restrict__ dgamma,
+                         short* __restrict__ dbeta,
+                         short* __restrict__ dbias) {
+  constexpr int NQ = DROP ? 3 : 2;
+  // LDS index of column c: c + c/8 — a lane's 8-column group starts 9
+  // words after its neighbour's, so the per-j accesses are conflict-free.
+  constexpr int LW = NCH * 576;
+  constexpr int SL = NQ * LW;  // one wave's accumulators
+  __shared__ float red[(NW / 2) * SL];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+
+  float gam[NCH][8], ag[NCH][8], ab[NCH][8], am[NCH][8];
+  bool act[NCH];
+#pragma unroll
+  for (int k = 0; k < NCH; ++k) {
+    const int c = lane * 8 + k * (WAVE * 8);
+    act[k] = c < D;
+    s16x8 gv = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (act[k]) gv = *(const s16x8*)(gamma + c);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      gam[k][j] = bfbits2f(gv[j]);
+      ag[k][j] = 0.f;
+      ab[k][j] = 0.f;
+      am[k][j] = 0.f;
+    }
+  }
+
+  // Row loop, software-pipelined one row deep: the next row's loads are
+  // issued before this row's math.  Every wave on the chip starts at once
+  // and does identical work, so without the prefetch the load, math and
+  // store phases of all waves line up and add instead of overlapping.
+  s16x8 dv[NCH], sv[NCH], dvn[NCH], svn[NCH];
+  unsigned long long mk[NCH], mkn[NCH];
+  float mu = 0.f, rs = 0.f, mun = 0.f, rsn = 0.f;
+  auto load_row = [&](int row, s16x8 (&d)[NCH], s16x8 (&x)[NCH],
+                      unsigned long long (&m)[NCH], float& mu_, float& rs_) {
+    const long base = (long)row * D;
+    mu_ = mean[row];
+    rs_ = rstd[row];
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+      const int c = lane * 8 + k * (WAVE * 8);
+      d[k] = s16x8{0, 0, 0, 0, 0, 0, 0, 0};
+      x[k] = d[k];
+      m[k] = 0;
+      if (act[k]) {
+        d[k] = *(const s16x8*)(dy + base + c);
+        x[k] = *(const s16x8*)(s + base + c);
+        if (DROP) m[k] = *(const unsigned long long*)(mask + base + c);
+      }
+    }
+  };
+  const int row0 = blockIdx.x * NW + wave, rstep = gridDim.x * NW;
+  if (row0 < R) load_row(row0, dvn, svn, mkn, mun, rsn);
+  for (int row = row0; row < R; row += rstep) {
+    const long base = (long)row * D;
+    mu = mun;
+    rs = rsn;
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+      dv[k] = dvn[k];
+      sv[k] = svn[k];
+      mk[k] = mkn[k];
+    }
+    if (row + rstep < R) load_row(row + rstep, dvn, svn, mkn, mun, rsn);
+    // Roundings are pinned to what ln_bwd_kernel compiles to (products
+    // rounded before the row sums; g - sg and - xh*sgx fused), so dx and
+    // dxm match the two-kernel path bit for bit whatever the optimizer
+    // would pick here.
+    float sg = 0.f, sgx = 0.f;
+    {
+#pragma clang fp contract(off)
+#pragma unroll
+      for (int k = 0; k < NCH; ++k) {
+        if (act[k]) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            float xh = (bfbits2f(sv[k][j]) - mu) * rs;
+            float g = bfbits2f(dv[k][j]) * gam[k][j];
+            float gx = g * xh;
+            sg += g;
+            sgx += gx;
+          }
+        }
+      }
+    }
+    sg = wave_sum(sg) / D;
+    sgx = wave_sum(sgx) / D;
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+      if (act[k]) {
+        const int c = lane * 8 + k * (WAVE * 8);
+        s16x8 xo, mo;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          float xh = (bfbits2f(sv[k][j]) - mu) * rs;
+          float dyv = bfbits2f(dv[k][j]);
+          float d = rs * __builtin_fmaf(-xh, sgx,
+                                        __builtin_fmaf(dyv, gam[k][j], -sg));
+          xo[j] = f2bfbits(d);
+          ag[k][j] = __builtin_fmaf(dyv, xh, ag[k][j]);
+          ab[k][j] += dyv;
+          if (DROP) {
+            mo[j] = ((mk[k] >> (8 * j)) & 0xff) ? f2bfbits(d * inv_keep)
+                                                : (short)0;
+            am[k][j] += bfbits2f(mo[j]);  // the ROUNDED value, as colsum
+          }
+        }
+        *(s16x8*)(dx + base + c) = xo;
+        if (DROP) *(s16x8*)(dxm + base + c) = mo;
+      }
+    }
+  }
+
+  // Block combine: a binary tree over the waves through LDS, registers
+  // to registers (the upper half of the live waves parks its accumulators,
+  // the lower half adds them).  LDS float atomics into one copy measured
+  // ~35 us per call for this step alone (docs/PERF.md).
+  auto park = [&](float* dst) {
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+      if (act[k]) {
+        const int li = (lane * 8 + k * (WAVE * 8)) / 8 * 9;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          dst[li + j] = ag[k][j];
+          dst[LW + li + j] = ab[k][j];
+          if (DROP) dst[2 * LW + li + j] = am[k][j];
+        }
+      }
+    }
+  };
+#pragma unroll
+  for (int half = NW / 2; half >= 1; half >>= 1) {
+    if (wave >= half && wave < 2 * half) park(red + (wave - half) * SL);
+    __syncthreads();
+    if (wave < half) {
+      const float* src = red + wave * SL;
+#pragma unroll
+      for (int k = 0; k < NCH; ++k) {
+        if (act[k]) {
+          const int li = (lane * 8 + k * (WAVE * 8)) / 8 * 9;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            ag[k][j] += src[li + j];
+            ab[k][j] += src[LW + li + j];
+            if (DROP) am[k][j] += src[2 * LW + li + j];
+          }
+        }
+      }
+    }
+    __syncthreads();
+  }
+  if (wave == 0) park(red);
+  __syncthreads();
+  // cross-block: one fp32 atomic per (quantity, column) per block
+  const int nflush = ((DROP && dbias) ? 3 : 2) * D;
+  const int rot = (int)((blockIdx.x * 64u) % (unsigned)nflush);
+  for (int i = threadIdx.x; i < nflush; i += NW * 64) {
+    int ii = i + rot;
+    if (ii >= nflush) ii -= nflush;
+    const int q = ii / D, c = ii - q * D;
+    atomicAdd(&ws[ii], red[q * LW + c + (c >> 3)]);
+  }
+  unsigned* cnt = (unsigned*)(ws + 3 * D);
+  if (last_arriver(cnt, gridDim.x)) {
+    for (int i = threadIdx.x; i < nflush; i += NW * 64) {
+      const int q = i / D, c = i - q * D;
+      (q == 0 ? dgamma : q == 1 ? dbeta : dbias)[c] = f2bfbits(ws[i]);
+      ws[i] = 0.f;
+    }
+    if (threadIdx.x == 0)
+      __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
 // ---------------------------------------------------------------------------
 // p > 0: dropout on x fused before the residual add; returns an extra
 // byte mask tensor.  seed_t (optional int64[1] device counter) keeps
@@ -305,16 +512,31 @@ std::vector<torch::Tensor> ln_fwd(torch::Tensor x, torch::Tensor res,
   return {y, s, mean, rstd};
 }
 
+// Implemented in gemm.hip.
+torch::Tensor colsum(torch::Tensor a, c10::optional<torch::Tensor> out);
+
 // mask given: additionally returns dxm = dx*mask*inv_keep (gradient of
 // the fused sublayer dropout input); dx is the residual-branch gradient.
+// dbias_out given with mask: also filled with colsum(dxm) — the bias
+// gradient of the linear feeding the dropout — and returned fifth.
+// Default is the one-pass ln_bwd_fused_kernel; D % 8 != 0 or D > 1024, or
+// TFMX_LN_BWD=split (A/B arm, read per call), run ln_bwd + ln_gb
+// (+ colsum).  TFMX_LN_BWD_WAVES=8 selects the 8-wave block variant.
 std::vector<torch::Tensor> ln_bwd(torch::Tensor dy, torch::Tensor s,
                                   torch::Tensor gamma, torch::Tensor mean,
                                   torch::Tensor rstd,
                                   c10::optional<torch::Tensor> dgamma_out,
                                   c10::optional<torch::Tensor> dbeta_out,
                                   c10::optional<torch::Tensor> mask,
-                                  double p) {
+                                  double p,
+                                  c10::optional<torch::Tensor> dbias_out) {
+  TORCH_CHECK(dy.is_cuda() && dy.dtype() == torch::kBFloat16 &&
+              dy.dim() == 2 && dy.is_contiguous() && s.is_contiguous() &&
+              s.sizes() == dy.sizes(), "ln_bwd: bad dy/s");
   const int R = dy.size(0), D = dy.size(1);
+  TORCH_CHECK(mean.numel() == R && rstd.numel() == R && gamma.numel() == D &&
+              (!mask.has_value() || mask->numel() == (long)R * D),
+              "ln_bwd: shape mismatch");
   auto dx = torch::empty_like(dy);
   auto dest = [&](c10::optional<torch::Tensor>& o) {
     if (o.has_value()) {
@@ -327,9 +549,56 @@ std::vector<torch::Tensor> ln_bwd(torch::Tensor dy, torch::Tensor s,
   auto dgamma = dest(dgamma_out);
   auto dbeta = dest(dbeta_out);
   auto stream = at::hip::getCurrentHIPStream();
-  torch::Tensor dxm;
-  if (mask.has_value()) {
-    dxm = torch::empty_like(dy);
+  const bool drop = mask.has_value();
+  torch::Tensor dxm, dbias;
+  if (drop) dxm = torch::empty_like(dy);
+  if (drop && dbias_out.has_value()) dbias = dest(dbias_out);
+  static std::map<std::pair<int, int>, torch::Tensor> ws_cache;
+  auto wkey = std::make_pair((int)dy.get_device(), D);
+  auto wit = ws_cache.find(wkey);
+  if (wit == ws_cache.end())
+    wit = ws_cache.emplace(wkey, torch::zeros(
+        {3L * D + 1}, dy.options().dtype(torch::kFloat32))).first;  // +cnt
+  const char* arm = getenv("TFMX_LN_BWD");
+  const bool split = arm && strcmp(arm, "split") == 0;
+  if (!split && D % 8 == 0 && D <= 1024 && R > 0) {
+    const char* wv = getenv("TFMX_LN_BWD_WAVES");
+    const bool w8 = wv && atoi(wv) == 8;
+    auto launch = [&](auto dropc, auto nchc, auto nwc) {
+      constexpr bool DR = decltype(dropc)::value;
+      constexpr int NCH = decltype(nchc)::value;
+      constexpr int NW = decltype(nwc)::value;
+      const int grid = std::min(LNF_ROWS_PER_PASS / NW, cdiv(R, NW));
+      ln_bwd_fused_kernel<DR, NCH, NW><<<grid, NW * 64, 0, stream>>>(
+          (const short*)dy.data_ptr(), (const short*)s.data_ptr(),
+          (const short*)gamma.data_ptr(), mean.data_ptr<float>(),
+          rstd.data_ptr<float>(), (short*)dx.data_ptr(), R, D,
+          DR ? mask->data_ptr<unsigned char>() : nullptr,
+          DR ? (short*)dxm.data_ptr() : nullptr,
+          DR ? 1.0f / (1.0f - (float)p) : 1.f,
+          wit->second.data_ptr<float>(), (short*)dgamma.data_ptr(),
+          (short*)dbeta.data_ptr(),
+          dbias.defined() ? (short*)dbias.data_ptr() : nullptr);
+    };
+    using T = std::true_type;
+    using F = std::false_type;
+    using C1 = std::integral_constant<int, 1>;
+    using C2 = std::integral_constant<int, 2>;
+    using W8 = std::integral_constant<int, 8>;
+    using W16 = std::integral_constant<int, 16>;
+    auto by_w = [&](auto dropc, auto nchc) {
+      if (w8) launch(dropc, nchc, W8{}); else launch(dropc, nchc, W16{});
+    };
+    auto by_ch = [&](auto dropc) {
+      // two chunks need > 128 VGPRs: 8 waves (512 threads) only
+      if (D <= 512) by_w(dropc, C1{}); else launch(dropc, C2{}, W8{});
+    };
+    if (drop) by_ch(T{}); else by_ch(F{});
+    if (dbias.defined()) return {dx, dgamma, dbeta, dxm, dbias};
+    if (drop) return {dx, dgamma, dbeta, dxm};
+    return {dx, dgamma, dbeta};
+  }
+  if (drop) {
     ln_bwd_kernel<true><<<cdiv(R, 4), 256, 0, stream>>>(
         (const short*)dy.data_ptr(), (const short*)s.data_ptr(),
         (const short*)gamma.data_ptr(), mean.data_ptr<float>(),
@@ -343,12 +612,8 @@ std::vector<torch::Tensor> ln_bwd(torch::Tensor dy, torch::Tensor s,
         rstd.data_ptr<float>(), (short*)dx.data_ptr(), R, D, nullptr,
         nullptr, 1.f);
   }
-  static std::map<std::pair<int, int>, torch::Tensor> ws_cache;
-  auto wkey = std::make_pair((int)dy.get_device(), D);
-  auto wit = ws_cache.find(wkey);
-  if (wit == ws_cache.end())
-    wit = ws_cache.emplace(wkey, torch::zeros(
-        {2L * D + 1}, dy.options().dtype(torch::kFloat32))).first;  // +cnt
+  // split path: [0, 2D] of the shared workspace (counter at word 2D);
+  // both paths leave every word they touch zero again
   auto acc_g = wit->second.narrow(0, 0, D);
   auto acc_b = wit->second.narrow(0, D, D + 1);
   // 64-thread blocks: at d_model=512 a 256-thread block grid is only 128
@@ -359,6 +624,7 @@ std::vector<torch::Tensor> ln_bwd(torch::Tensor dy, torch::Tensor s,
       mean.data_ptr<float>(), rstd.data_ptr<float>(),
       acc_g.data_ptr<float>(), acc_b.data_ptr<float>(),
       (short*)dgamma.data_ptr(), (short*)dbeta.data_ptr(), R, D);
-  if (mask.has_value()) return {dx, dgamma, dbeta, dxm};
+  if (dbias.defined()) return {dx, dgamma, dbeta, dxm, colsum(dxm, dbias)};
+  if (drop) return {dx, dgamma, dbeta, dxm};
   return {dx, dgamma, dbeta};
 }

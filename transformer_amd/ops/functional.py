@@ -564,6 +564,205 @@ class _DropResidualLNFlatFn(torch.autograd.Function):
         return dxm, dres, None, None, None
 
 
+# ---------------------------------------------------------------------------
+# Sublayer composites: LN(dropout(linear(x)) + res) and the whole FFN block
+# as ONE autograd node each.  Forward runs the same kernels as the separate
+# ops (same dropout-seed draws, same order).  Backward starts from the
+# one-pass ln_bwd, which already streams dxm — the dY of the linear — and
+# so delivers that linear's bias gradient for free (no colsum re-read);
+# the FFN block can additionally apply the ReLU mask and the residual-branch
+# add in the two dX GEMM epilogues (TFMX_FFN_BWD=fused, default off).
+# ---------------------------------------------------------------------------
+
+def _ln_drop_fwd(E, a, res, gamma, beta, eps, p):
+    if _GRAPH_SEED_T is not None:
+        _GRAPH_SALT[0] += 1
+        return E.ln_fwd(a, res, gamma, beta, eps, p, _GRAPH_SALT[0],
+                        _GRAPH_SEED_T)
+    seed = int(torch.randint(0, 2**31 - 1, (1,)).item())
+    return E.ln_fwd(a, res, gamma, beta, eps, p, seed)
+
+
+def _grad_dst(p, flat):
+    """Destination for a 1-D parameter gradient: the flat-buffer view, or
+    a fresh tensor handed back to autograd."""
+    if p is None:
+        return None
+    return _flat(p).view(-1) if flat else torch.empty_like(p)
+
+
+def _ln_drop_bwd(E, ctx, dy, s, gamma, mean, rstd, mask, g, bt, b):
+    """Fused ln_bwd writing dgamma/dbeta/db to their destinations.
+    Returns (dres, dxm, dgamma, dbeta, db)."""
+    flat = ctx.flat
+    dg, dbt, db = _grad_dst(g, flat), _grad_dst(bt, flat), _grad_dst(b, flat)
+    out = E.ln_bwd(dy.contiguous(), s, gamma, mean, rstd, dg, dbt, mask,
+                   ctx.p, db)
+    if flat:
+        _grad_ready(g, bt)
+    return out[0], out[3], dg, dbt, db
+
+
+class _LinearDropLNFn(torch.autograd.Function):
+    """y = LN(dropout(x @ W^T + b) + res)."""
+
+    @staticmethod
+    def forward(ctx, x, res, w, b, gamma, beta, p, eps):
+        E = ext()
+        a = _fwd_gemm(E, x, w, b, None)
+        y, s, mean, rstd, mask = _ln_drop_fwd(E, a, res, gamma, beta, eps, p)
+        ctx.p = p
+        ctx.flat = False
+        ctx.params = (w, b, gamma, beta)
+        ctx.save_for_backward(x, s, mean, rstd, mask)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        E = ext()
+        x, s, mean, rstd, mask = ctx.saved_tensors
+        w, b, g, bt = ctx.params
+        dres, dxm, dg, dbt, db = _ln_drop_bwd(E, ctx, dy, s, g, mean, rstd,
+                                              mask, g, bt, b)
+        dx = _dx_gemm(E, dxm, w)
+        if ctx.flat:
+            _dw_gemm(dxm, x, out=_flat(w).view(w.shape[0], -1))
+            _grad_ready(w, b)
+            return dx, dres, None, None, None
+        dw = _dw_gemm(dxm, x)
+        return dx, dres, dw, db, dg, dbt, None, None
+
+
+class _LinearDropLNFlatFn(torch.autograd.Function):
+    """Same, parameters [w, b, gamma, beta] hidden from autograd; their
+    gradients land in the flat buffer."""
+
+    @staticmethod
+    def forward(ctx, x, res, params, p, eps):
+        y = _LinearDropLNFn.forward(ctx, x, res, *params, p, eps)
+        ctx.flat = True
+        return y
+
+    backward = staticmethod(_LinearDropLNFn.backward)
+
+
+def _dx_epilogue_ok(E, M, n_out, k):
+    """Whether the dX GEMM (M, n_out, k) would run on the gemm256 kernel —
+    the only one carrying the relu-mask / residual-add epilogues — through
+    the cached-W^T backend.  Opt-in, TFMX_FFN_BWD=fused (A/B arm, read per
+    call): with the aux tensor read in the epilogue's 2-byte store pattern
+    behind a 1-block/CU main loop, both fused GEMMs measured SLOWER than
+    GEMM + separate pass (docs/PERF.md), so the default stays split."""
+    return (os.environ.get("TFMX_FFN_BWD", "split") == "fused"
+            and _DX_BACKEND == "wt" and M >= 2048
+            and n_out % 64 == 0 and k % 64 == 0
+            and E.gemm256_viable(M, n_out, k))
+
+
+class _FFNDropLNFn(torch.autograd.Function):
+    """y = LN(dropout(relu(x @ W1^T + b1) @ W2^T + b2) + x)."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, gamma, beta, p, eps):
+        E = ext()
+        h = _fwd_gemm(E, x, w1, b1, "relu")
+        a = _fwd_gemm(E, h, w2, b2, None)
+        y, s, mean, rstd, mask = _ln_drop_fwd(E, a, x, gamma, beta, eps, p)
+        ctx.p = p
+        ctx.flat = False
+        ctx.params = (w1, b1, w2, b2, gamma, beta)
+        ctx.save_for_backward(x, h, s, mean, rstd, mask)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        E = ext()
+        x, h, s, mean, rstd, mask = ctx.saved_tensors
+        w1, b1, w2, b2, g, bt = ctx.params
+        flat = ctx.flat
+        dres, dxm, dg, dbt, db2 = _ln_drop_bwd(E, ctx, dy, s, g, mean, rstd,
+                                               mask, g, bt, b2)
+        dw2 = _dw_gemm(dxm, h, out=_flat(w2).view(w2.shape[0], -1)
+                       if flat else None)
+        if flat:
+            _grad_ready(w2, b2)
+        M, d, dff = x.shape[0], x.shape[1], h.shape[1]
+        nob = torch.Tensor()
+        if _dx_epilogue_ok(E, M, dff, d):
+            # dz = (dxm @ W2) * (h > 0), mask applied on the accumulators
+            dz = E.gemm256_nt(dxm, _wt_padded(E, w2), nob, 2, None, h)
+        else:
+            dz = E.relu_bwd(_dx_gemm(E, dxm, w2).contiguous(), h)
+        dw1 = _dw_gemm(dz, x, out=_flat(w1).view(w1.shape[0], -1)
+                       if flat else None)
+        db1 = E.colsum(dz, _grad_dst(b1, flat)) if b1 is not None else None
+        if flat:
+            _grad_ready(w1, b1)
+        if _dx_epilogue_ok(E, M, d, dff):
+            # dx = dz @ W1 + dres in one rounding
+            dx = E.gemm256_nt(dz, _wt_padded(E, w1), nob, 3, None, dres)
+        else:
+            dx = _dx_gemm(E, dz, w1) + dres
+        if flat:
+            return dx, None, None, None
+        return dx, dw1, db1, dw2, db2, dg, dbt, None, None
+
+
+class _FFNDropLNFlatFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, params, p, eps):
+        y = _FFNDropLNFn.forward(ctx, x, *params, p, eps)
+        ctx.flat = True
+        return y
+
+    backward = staticmethod(_FFNDropLNFn.backward)
+
+
+def _all_flat(*params):
+    fl = [_flat(p) is not None for p in params if p is not None]
+    return all(fl), any(fl)
+
+
+def linear_dropout_residual_layernorm(x, w, b, res, gamma, beta, rate: float,
+                                      training: bool, eps: float = 1e-6):
+    """LN(dropout(x @ W^T + b) + res) — an attention block's output
+    projection together with its post-sublayer dropout + residual LN.  One
+    autograd node on GPU when training with rate > 0; otherwise (CPU, eval,
+    rate 0, or only some parameters flat) the two separate ops."""
+    allf, anyf = _all_flat(w, b, gamma, beta)
+    if not (x.is_cuda and training and rate > 0.0 and allf == anyf):
+        return dropout_residual_layernorm(linear(x, w, b), res, gamma, beta,
+                                          rate, training, eps)
+    shp = res.shape
+    x2 = x.reshape(-1, x.shape[-1]).contiguous()
+    r2 = res.reshape(-1, shp[-1]).contiguous()
+    if allf:
+        y = _LinearDropLNFlatFn.apply(x2, r2, [w, b, gamma, beta], rate, eps)
+    else:
+        y = _LinearDropLNFn.apply(x2, r2, w, b, gamma, beta, rate, eps)
+    return y.view(shp)
+
+
+def ffn_dropout_residual_layernorm(x, w1, b1, w2, b2, gamma, beta,
+                                   rate: float, training: bool,
+                                   eps: float = 1e-6):
+    """LN(dropout(relu(x @ W1^T + b1) @ W2^T + b2) + x) — the whole
+    position-wise FFN sublayer; same fallback rule as above."""
+    allf, anyf = _all_flat(w1, b1, w2, b2, gamma, beta)
+    if not (x.is_cuda and training and rate > 0.0 and allf == anyf):
+        h = linear(x, w1, b1, activation="relu")
+        return dropout_residual_layernorm(linear(h, w2, b2), x, gamma, beta,
+                                          rate, training, eps)
+    shp = x.shape
+    x2 = x.reshape(-1, shp[-1]).contiguous()
+    if allf:
+        y = _FFNDropLNFlatFn.apply(x2, [w1, b1, w2, b2, gamma, beta], rate,
+                                   eps)
+    else:
+        y = _FFNDropLNFn.apply(x2, w1, b1, w2, b2, gamma, beta, rate, eps)
+    return y.view(shp)
+
+
 def residual_layernorm(x, res, gamma, beta, eps: float = 1e-6):
     if x.is_cuda:
         shp = x.shape
