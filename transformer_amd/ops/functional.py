@@ -18,12 +18,22 @@ from __future__ import annotations
 
 import math
 
-import os
-
 import torch
 
 from . import reference as R
 from . import ext
+from .gemm_dispatch import (  # noqa: F401  (re-exported: graph.py, optimizer,
+    bump_weight_version,      # models and tests reach for them here)
+    prepare_weight_caches,
+    set_capture_hint,
+    _dense2d,
+    _dw_db_gemm,
+    _dw_gemm,
+    _dx_epilogue_ok,
+    _dx_gemm,
+    _fwd_gemm,
+    _wt_padded,
+)
 
 
 # ---------------------------------------------------------------------------
@@ -63,213 +73,88 @@ def _flat(p):
     return getattr(p, "_flat_grad", None) if p is not None else None
 
 
+# Each autograd Function below has ONE body for both modes.  Its parameter
+# slots hold the tensors in autograd mode and None in flat mode, where the
+# parameters travel in the `hidden` list instead (a list is opaque to
+# autograd, so only the activations are differentiable).  backward hands
+# every gradient kernel its destination from _grad_dst, then in flat mode
+# fires _grad_ready and returns None in the parameter slots.
+
+def _slots(flat, *params):
+    """The (*parameter slots, hidden) arguments of apply()."""
+    if flat:
+        return (None,) * len(params) + (list(params),)
+    return params + (None,)
+
+
+def _grad_dst(p, flat):
+    """Where the backward kernel writes parameter `p`'s gradient: p's slice
+    of the flat buffer (a matrix as 2-D rows, a vector 1-D), or a fresh
+    tensor that backward hands back to autograd."""
+    if p is None:
+        return None
+    if not flat:
+        return torch.empty_like(p)
+    fg = p._flat_grad
+    return fg.view(p.shape[0], -1) if p.dim() > 1 else fg.view(-1)
+
+
+# ---------------------------------------------------------------------------
+# Dropout seeds (K11): from the torch RNG, or from a device counter under
+# HIP-graph capture (SURVEY.md Q12).  While a step is being captured the
+# seed must come from a DEVICE counter (advanced in-graph by the optimizer's
+# adam_coefs kernel) — a host seed would be baked into the graph and every
+# replay would reuse the same mask.  Each call site gets a distinct salt
+# (capture order is deterministic).
+# ---------------------------------------------------------------------------
+
+_GRAPH_SEED_T = None
+_GRAPH_SALT = [0]
+
+
+def set_graph_rng(seed_tensor):
+    """Install (or clear, with None) the device seed tensor used by dropout
+    during graph capture."""
+    global _GRAPH_SEED_T
+    _GRAPH_SEED_T = seed_tensor
+    _GRAPH_SALT[0] = 0
+
+
+def _dropout_seed():
+    """The trailing (seed, seed_t) arguments of E.ln_fwd / E.dropout_fwd for
+    ONE dropout site: the next salt plus the device seed tensor under graph
+    capture, otherwise one host draw from the torch RNG."""
+    if _GRAPH_SEED_T is not None:
+        _GRAPH_SALT[0] += 1
+        return _GRAPH_SALT[0], _GRAPH_SEED_T
+    return int(torch.randint(0, 2**31 - 1, (1,)).item()), None
+
+
 # ---------------------------------------------------------------------------
 # Linear: y = x @ W^T + b, optional fused ReLU epilogue (K1/K7/K8/K12).
+# Backend choice per GEMM: gemm_dispatch.py.
 # ---------------------------------------------------------------------------
-
-
-# GEMM backend (round 2): every training-shape GEMM runs hand-written.
-# Forward goes to the gemm256/128 NT dispatch (measured best hand path:
-# 600-1040 TF; the uni counted-vmcnt schedule variants measured slower —
-# see gemm_uni.hip header); dX and the wide dW go to the gemm_uni TR-mode
-# kernels (tr16 transpose-read operands).  hipBLASLt remains only as the
-# TFMX_FWD_GEMM=blaslt A/B arm; TFMX_FWD_GEMM=uni forces uni NT forward.
-_FWD_BACKEND = os.environ.get("TFMX_FWD_GEMM", "hand")
-_FWD_HIP = _FWD_BACKEND == "hip"
-
-
-# Version counter for weight-derived caches (the padded-transposed logits
-# weight): bumped by NoamAdam.step so caches refresh once per step.
-_WEIGHT_VERSION = [0]
-
-
-def bump_weight_version():
-    _WEIGHT_VERSION[0] += 1
-
-
-_WTP_CACHE: dict = {}  # id(weight) -> [version, buf, weight]
-_WTP_TABLE = [None]    # cached transpose_batch descriptor table
-# A captured hipGraph holds the table ADDRESS it recorded; if the registry
-# grows later and the table is rebuilt, the old tensor must stay alive or
-# replays would read freed memory.
-_WTP_TABLES_KEEP: list = []
-
-
-def _build_wtp_table(device):
-    rows = []
-    for ver, buf, w in _WTP_CACHE.values():
-        M, N = w.shape
-        ldo = buf.stride(0)
-        for bm in range(0, M, 64):
-            for bn in range(0, N, 64):
-                rows.append([w.data_ptr(), buf.data_ptr(), M, N, ldo,
-                             bm, bn])
-    t = torch.tensor(rows, dtype=torch.int64).to(device)
-    _WTP_TABLES_KEEP.append(t)
-    return t
-
-
-def prepare_weight_caches():
-    """Build the transpose_batch descriptor table eagerly (it involves a
-    host->device copy, which is illegal inside hipGraph capture) — called
-    by CapturedTrainStep between warmup and capture."""
-    if _WTP_CACHE and _WTP_TABLE[0] is None:
-        dev = next(iter(_WTP_CACHE.values()))[1].device
-        _WTP_TABLE[0] = _build_wtp_table(dev)
-
-
-def _wt_padded(E, w, gran=64):
-    """W[N,K]^T into a (K, Np) buffer, Np = N rounded up to `gran` (pad
-    columns zero) — the NT B-operand for dX.  gran=256 matches ce_bwd's
-    padded dlogits contraction (the ragged-vocab head); the generic path
-    uses 64 (the GEMM K-step) so the contraction equals dY's width.  All
-    registered buffers refresh together in ONE transpose_batch launch per
-    optimizer step (bump_weight_version) — a captured step records that
-    launch, so graph replays refresh too (graph.py bumps before capture)."""
-    key = id(w)
-    ent = _WTP_CACHE.get(key)
-    npad = (w.shape[0] + gran - 1) // gran * gran
-    if ent is None or ent[1].shape[1] != npad:
-        buf = torch.zeros(w.shape[1], npad, device=w.device, dtype=w.dtype)
-        ent = [_WEIGHT_VERSION[0], buf, w]
-        _WTP_CACHE[key] = ent
-        _WTP_TABLE[0] = None  # registry changed; rebuild lazily
-        E.transpose2d_into(w, buf)
-        return buf
-    if ent[0] != _WEIGHT_VERSION[0]:
-        if _WTP_TABLE[0] is None:
-            _WTP_TABLE[0] = _build_wtp_table(w.device)
-        E.transpose_batch(_WTP_TABLE[0])
-        v = _WEIGHT_VERSION[0]
-        for e in _WTP_CACHE.values():
-            e[0] = v
-    return ent[1]
-
-
-_CAPTURE_HINT = False
-
-
-def set_capture_hint(on: bool):
-    """Inside a hipGraph (GraphedDecoder) launch overhead is replayed
-    away and the library kernels win even at M=B rows (0.705 vs 0.788
-    ms/token); eager small-M calls keep the cheap-launch hand-written
-    kernel.  Set around warmup+capture so both trace the same path."""
-    global _CAPTURE_HINT
-    _CAPTURE_HINT = on
-
-
-def _fwd_gemm(E, x, w, b, activation):
-    epi = 1 if activation == "relu" else 0
-    if _FWD_BACKEND == "blaslt" and b is not None and \
-            (x.shape[0] > 1024 or _CAPTURE_HINT):
-        # A/B arm: hipBLASLt fused bias/ReLU epilogues (round-1 default)
-        if activation == "relu":
-            if hasattr(torch, "_addmm_activation"):
-                return torch._addmm_activation(b, x, w.t())
-            return torch.relu(torch.nn.functional.linear(x, w, b))
-        return torch.nn.functional.linear(x, w, b)
-    if _FWD_BACKEND == "uni" and E.gemm_uni_viable(x.shape[0], w.shape[0],
-                                                   x.shape[1]):
-        return E.gemm_uni_nt(x, w, b, epi)
-    # default: gemm256/128 dispatch (best-measured hand-written NT path;
-    # launch is cheaper than the library's at small M, decode/serving)
-    return E.gemm_nt(x, w, b if b is not None else torch.Tensor(), epi)
-
-def _dw_gemm(dy, x, out=None):
-    """dW[N,K] = dY^T @ X — plain GEMM, hand-written both ways: the wide
-    logits head goes to the deep-pipelined TRxTR gemm_uni_tn (both
-    operands tr16 transpose-read), the d_model-sized heads to the
-    split-contraction gemm_dw kernel (tools/gemm_bench.py)."""
-    E = ext()
-    npad = (dy.shape[1] + 255) // 256 * 256
-    if dy.shape[1] >= 8192 and dy.shape[0] % 64 == 0 \
-            and (dy.shape[1] % 256 == 0 or dy.stride(0) >= npad) \
-            and x.shape[1] % 128 == 0:
-        N = dy.shape[1]
-        main = (N // 256) * 256
-        if main != N and main > 0:
-            if out is None:
-                out = torch.empty(N, x.shape[1], device=dy.device,
-                                  dtype=dy.dtype)
-            # Grid-quantization cliff: ceil(N/256) tiles puts the grid a
-            # couple of blocks past 256 (one per CU at this kernel's LDS),
-            # and the stragglers cost a whole second pass.  Compute the
-            # 256-aligned main span at exactly one block wave, then the
-            # ragged vocab tail (a few rows, full contraction) split-K so
-            # it also fills the chip for its instant of work.
-            E.gemm_uni_tn(dy[:, :main], x, out[:main], 1)
-            E.gemm_uni_tn(dy[:, main:], x, out[main:], 64)
-            return out
-        return E.gemm_uni_tn(dy, x, out)
-    # gemm_dw writes DISJOINT per-slice fp32 partials (no atomics, no
-    # zeroing — the fp32-atomic epilogue measured at the chip's atomic
-    # rate); it sizes its own torch::empty workspace via the caching
-    # allocator, so no Python-side workspace is needed.
-    return E.gemm_dw(dy.contiguous(), x, out, None, None)
-
-
-# dX backend: "wt" contracts against a per-step cached transposed weight
-# through the fast NT path; "uni" reads W red-major via tr16 (no
-# transpose); "blaslt" is the library A/B arm.  Default = measured winner.
-_DX_BACKEND = os.environ.get("TFMX_DX", "wt")
-
-
-def _dx_gemm(E, dy, w):
-    """dX[M,K] = dY[M,N] @ W[N,K] — hand-written: either NT against the
-    cached W^T (refreshed once per optimizer step) or NTxTR with W read
-    red-major via tr16.  The ragged-vocab head's dY arrives as ce_bwd's
-    zero-padded row-strided view; the contraction widens to the 64-aligned
-    pad (zero columns) against the padded-transposed weight."""
-    N = w.shape[0]
-    M = dy.shape[0]
-    if _DX_BACKEND == "blaslt":
-        return torch.matmul(dy, w)
-    npad = (N + 255) // 256 * 256
-    padded = (npad != N and dy.stride(1) == 1 and dy.stride(0) == npad
-              and dy.storage_offset() == 0)
-    if padded and E.gemm_uni_viable(M, w.shape[1], npad):
-        full = dy.as_strided((M, npad), (npad, 1))
-        return E.gemm_nt(full, _wt_padded(E, w, 256), torch.Tensor(), 0)
-    if _DX_BACKEND == "wt" and N % 64 == 0 and M >= 2048:
-        return E.gemm_nt(_dense2d(dy), _wt_padded(E, w), torch.Tensor(), 0)
-    if N % 64 == 0 and E.gemm_uni_viable(M, w.shape[1], N):
-        return E.gemm_uni_nn(dy, w)
-    return torch.matmul(dy, w)  # small/odd shapes (not a training shape)
-
-
-def _dense2d(t):
-    """Row-strided dense (stride(1)==1) passes through — ce_bwd's padded
-    dlogits view must NOT be copied back to contiguous."""
-    return t if (t.stride(1) == 1 and t.stride(0) >= t.shape[1]) \
-        else t.contiguous()
-
-
-def _dw_db_gemm(dy, x, has_bias, w_out=None, b_out=None):
-    """dW and (optionally) db together.  gemm_dw CAN fuse db into its dY
-    stream, but the fused variant costs 138 vs 116 VGPRs — one whole
-    workgroup of block-level overlap per CU — and measured slower
-    end-to-end than a separate colsum pass, so db stays separate."""
-    E = ext()
-    dw = _dw_gemm(dy, x, out=w_out)
-    db = E.colsum(dy, b_out) if has_bias else None
-    return dw, db
-
 
 class _LinearFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, b, activation):
+    def forward(ctx, x, w, b, hidden, activation):
         # x: (M, K) bf16; w: (N, K) bf16; b: (N,) bf16 or None
         E = ext()
+        ctx.flat = hidden is not None
+        if ctx.flat:
+            w, b = hidden
         y = _fwd_gemm(E, x, w, b, activation)
         ctx.activation = activation
-        ctx.has_bias = b is not None
-        ctx.save_for_backward(x, w, y if activation == "relu" else torch.Tensor())
+        ctx.params = (w, b)
+        ctx.save_for_backward(x, y if activation == "relu" else torch.Tensor())
         return y
 
     @staticmethod
     def backward(ctx, dy):
         E = ext()
-        x, w, y = ctx.saved_tensors
+        x, y = ctx.saved_tensors
+        w, b = ctx.params
+        flat = ctx.flat
         if ctx.activation == "relu":
             # (A fused relu+colsum kernel — relu_bwd_db — was built and
             # measured SLOWER in context at every grid shape: the column-
@@ -280,42 +165,12 @@ class _LinearFn(torch.autograd.Function):
         else:
             dy = _dense2d(dy)
         dx = _dx_gemm(E, dy, w)         # dX[M,K] = dY[M,N] @ W[N,K]
-        dw, db = _dw_db_gemm(dy, x, ctx.has_bias)
-        return dx, dw, db, None
-
-
-class _LinearFlatFn(torch.autograd.Function):
-    """Linear whose weight/bias grads go straight into flat-buffer views.
-
-    w/b arrive hidden inside a list so autograd treats only x as
-    differentiable; backward writes dW/db into `p._flat_grad` (the kernels'
-    `out` argument) and fires the DP readiness callback."""
-
-    @staticmethod
-    def forward(ctx, x, wb, activation):
-        E = ext()
-        w, b = wb
-        y = _fwd_gemm(E, x, w, b, activation)
-        ctx.activation = activation
-        ctx.wb = wb
-        ctx.save_for_backward(x, y if activation == "relu" else torch.Tensor())
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        E = ext()
-        x, y = ctx.saved_tensors
-        w, b = ctx.wb
-        if ctx.activation == "relu":
-            dy = E.relu_bwd(dy.contiguous(), y)
-        else:
-            dy = _dense2d(dy)
-        dx = _dx_gemm(E, dy, w)
-        _dw_db_gemm(dy, x, b is not None,
-                    w_out=_flat(w).view(w.shape[0], -1),
-                    b_out=_flat(b).view(-1) if b is not None else None)
-        _grad_ready(w, b)
-        return dx, None, None
+        dw, db = _dw_db_gemm(dy, x, b is not None, w_out=_grad_dst(w, flat),
+                             b_out=_grad_dst(b, flat))
+        if flat:
+            _grad_ready(w, b)
+            dw = db = None
+        return dx, dw, db, None, None
 
 
 def linear(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor | None = None,
@@ -324,10 +179,8 @@ def linear(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor | None = None,
     if x.is_cuda:
         shp = x.shape
         x2 = x.reshape(-1, shp[-1]).contiguous()
-        if _flat(w) is not None:
-            y = _LinearFlatFn.apply(x2, [w, b], activation)
-        else:
-            y = _LinearFn.apply(x2, w, b, activation)
+        y = _LinearFn.apply(x2, *_slots(_flat(w) is not None, w, b),
+                            activation)
         return y.view(*shp[:-1], w.shape[0])
     y = torch.nn.functional.linear(x, w, b)
     if activation == "relu":
@@ -473,146 +326,80 @@ def fused_attention(q, k, v, kv_pad=None, causal=False, return_weights=False):
 
 
 # ---------------------------------------------------------------------------
-# Fused residual-add + LayerNorm, eps=1e-6 (K9).
-# ---------------------------------------------------------------------------
-
-class _ResidualLNFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, res, gamma, beta, eps):
-        E = ext()
-        y, s, mean, rstd = E.ln_fwd(x, res, gamma, beta, eps)
-        ctx.save_for_backward(s, gamma, mean, rstd)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        E = ext()
-        s, gamma, mean, rstd = ctx.saved_tensors
-        dx, dgamma, dbeta = E.ln_bwd(dy.contiguous(), s, gamma, mean, rstd)
-        # d/dx and d/dres are identical (y = LN(x + res))
-        return dx, dx, dgamma, dbeta, None
-
-
-class _ResidualLNFlatFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, res, gb, eps):
-        E = ext()
-        gamma, beta = gb
-        y, s, mean, rstd = E.ln_fwd(x, res, gamma, beta, eps)
-        ctx.gb_params = gb
-        ctx.save_for_backward(s, gamma, mean, rstd)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        E = ext()
-        s, gamma, mean, rstd = ctx.saved_tensors
-        g, b = ctx.gb_params
-        dx, _, _ = E.ln_bwd(dy.contiguous(), s, gamma, mean, rstd,
-                            _flat(g).view(-1), _flat(b).view(-1))
-        _grad_ready(g, b)
-        return dx, dx, None, None
-
-
-class _DropResidualLNFn(torch.autograd.Function):
-    """y = LN(dropout(x) + res): the sublayer dropout fused into the LN
-    kernels — no standalone dropout read/write of the (B,S,d) tensor in
-    either direction."""
-
-    @staticmethod
-    def forward(ctx, x, res, gamma, beta, p, eps):
-        E = ext()
-        if _GRAPH_SEED_T is not None:
-            _GRAPH_SALT[0] += 1
-            y, s, mean, rstd, mask = E.ln_fwd(x, res, gamma, beta, eps, p,
-                                              _GRAPH_SALT[0], _GRAPH_SEED_T)
-        else:
-            seed = int(torch.randint(0, 2**31 - 1, (1,)).item())
-            y, s, mean, rstd, mask = E.ln_fwd(x, res, gamma, beta, eps, p,
-                                              seed)
-        ctx.p = p
-        ctx.flat_gb = None
-        ctx.save_for_backward(s, gamma, mean, rstd, mask)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        E = ext()
-        s, gamma, mean, rstd, mask = ctx.saved_tensors
-        if ctx.flat_gb is not None:
-            g, b = ctx.flat_gb
-            dres, _, _, dxm = E.ln_bwd(dy.contiguous(), s, gamma, mean, rstd,
-                                       _flat(g).view(-1), _flat(b).view(-1),
-                                       mask, ctx.p)
-            _grad_ready(g, b)
-            return dxm, dres, None, None, None, None
-        dres, dgamma, dbeta, dxm = E.ln_bwd(dy.contiguous(), s, gamma, mean,
-                                            rstd, None, None, mask, ctx.p)
-        return dxm, dres, dgamma, dbeta, None, None
-
-
-class _DropResidualLNFlatFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, res, gb, p, eps):
-        y = _DropResidualLNFn.forward(ctx, x, res, gb[0], gb[1], p, eps)
-        ctx.flat_gb = gb
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        dxm, dres, _, _, _, _ = _DropResidualLNFn.backward(ctx, dy)
-        return dxm, dres, None, None, None
-
-
-# ---------------------------------------------------------------------------
-# Sublayer composites: LN(dropout(linear(x)) + res) and the whole FFN block
-# as ONE autograd node each.  Forward runs the same kernels as the separate
-# ops (same dropout-seed draws, same order).  Backward starts from the
-# one-pass ln_bwd, which already streams dxm — the dY of the linear — and
-# so delivers that linear's bias gradient for free (no colsum re-read);
-# the FFN block can additionally apply the ReLU mask and the residual-branch
-# add in the two dX GEMM epilogues (TFMX_FFN_BWD=fused, default off).
+# Fused (dropout +) residual-add + LayerNorm, eps=1e-6 (K9), alone and as
+# the tail of the sublayer composites: LN(dropout(linear(x)) + res) and the
+# whole FFN block as ONE autograd node each.  The composites' forward runs
+# the same kernels as the separate ops (same dropout-seed draws, same
+# order).  Backward starts from the one-pass ln_bwd, which already streams
+# dxm — the dY of the linear — and so delivers that linear's bias gradient
+# for free (no colsum re-read); the FFN block can additionally apply the
+# ReLU mask and the residual-branch add in the two dX GEMM epilogues
+# (TFMX_FFN_BWD=fused, default off).
 # ---------------------------------------------------------------------------
 
 def _ln_drop_fwd(E, a, res, gamma, beta, eps, p):
-    if _GRAPH_SEED_T is not None:
-        _GRAPH_SALT[0] += 1
-        return E.ln_fwd(a, res, gamma, beta, eps, p, _GRAPH_SALT[0],
-                        _GRAPH_SEED_T)
-    seed = int(torch.randint(0, 2**31 - 1, (1,)).item())
-    return E.ln_fwd(a, res, gamma, beta, eps, p, seed)
+    """(y, s, mean, rstd, mask) of LN(dropout(a) + res); p == 0 is the
+    plain residual LN: no seed drawn, mask None."""
+    if p > 0.0:
+        return E.ln_fwd(a, res, gamma, beta, eps, p, *_dropout_seed())
+    return (*E.ln_fwd(a, res, gamma, beta, eps), None)
 
 
-def _grad_dst(p, flat):
-    """Destination for a 1-D parameter gradient: the flat-buffer view, or
-    a fresh tensor handed back to autograd."""
-    if p is None:
-        return None
-    return _flat(p).view(-1) if flat else torch.empty_like(p)
-
-
-def _ln_drop_bwd(E, ctx, dy, s, gamma, mean, rstd, mask, g, bt, b):
-    """Fused ln_bwd writing dgamma/dbeta/db to their destinations.
-    Returns (dres, dxm, dgamma, dbeta, db)."""
+def _ln_drop_bwd(E, ctx, dy, s, mean, rstd, mask, g, bt, b=None):
+    """Fused ln_bwd writing dgamma/dbeta (and the bias gradient db of the
+    linear feeding the dropout) to their destinations.
+    Returns (dres, dxm, dgamma, dbeta, db); without dropout dxm is dres."""
     flat = ctx.flat
     dg, dbt, db = _grad_dst(g, flat), _grad_dst(bt, flat), _grad_dst(b, flat)
-    out = E.ln_bwd(dy.contiguous(), s, gamma, mean, rstd, dg, dbt, mask,
-                   ctx.p, db)
+    out = E.ln_bwd(dy.contiguous(), s, g, mean, rstd, dg, dbt, mask, ctx.p,
+                   db)
     if flat:
         _grad_ready(g, bt)
-    return out[0], out[3], dg, dbt, db
+    return out[0], out[3] if mask is not None else out[0], dg, dbt, db
+
+
+class _ResidualLNFn(torch.autograd.Function):
+    """y = LN(dropout(x) + res): the sublayer dropout fused into the LN
+    kernels — no standalone dropout read/write of the (B,S,d) tensor in
+    either direction.  p = 0: y = LN(x + res)."""
+
+    @staticmethod
+    def forward(ctx, x, res, gamma, beta, hidden, p, eps):
+        E = ext()
+        ctx.flat = hidden is not None
+        if ctx.flat:
+            gamma, beta = hidden
+        y, s, mean, rstd, mask = _ln_drop_fwd(E, x, res, gamma, beta, eps, p)
+        ctx.p = p
+        ctx.params = (gamma, beta)
+        ctx.save_for_backward(s, mean, rstd, mask)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        E = ext()
+        s, mean, rstd, mask = ctx.saved_tensors
+        g, bt = ctx.params
+        # without dropout d/dx and d/dres are identical (y = LN(x + res))
+        dres, dxm, dg, dbt, _ = _ln_drop_bwd(E, ctx, dy, s, mean, rstd, mask,
+                                             g, bt)
+        if ctx.flat:
+            dg = dbt = None
+        return dxm, dres, dg, dbt, None, None, None
 
 
 class _LinearDropLNFn(torch.autograd.Function):
     """y = LN(dropout(x @ W^T + b) + res)."""
 
     @staticmethod
-    def forward(ctx, x, res, w, b, gamma, beta, p, eps):
+    def forward(ctx, x, res, w, b, gamma, beta, hidden, p, eps):
         E = ext()
+        ctx.flat = hidden is not None
+        if ctx.flat:
+            w, b, gamma, beta = hidden
         a = _fwd_gemm(E, x, w, b, None)
         y, s, mean, rstd, mask = _ln_drop_fwd(E, a, res, gamma, beta, eps, p)
         ctx.p = p
-        ctx.flat = False
         ctx.params = (w, b, gamma, beta)
         ctx.save_for_backward(x, s, mean, rstd, mask)
         return y
@@ -622,68 +409,45 @@ class _LinearDropLNFn(torch.autograd.Function):
         E = ext()
         x, s, mean, rstd, mask = ctx.saved_tensors
         w, b, g, bt = ctx.params
-        dres, dxm, dg, dbt, db = _ln_drop_bwd(E, ctx, dy, s, g, mean, rstd,
-                                              mask, g, bt, b)
+        flat = ctx.flat
+        dres, dxm, dg, dbt, db = _ln_drop_bwd(E, ctx, dy, s, mean, rstd, mask,
+                                              g, bt, b)
         dx = _dx_gemm(E, dxm, w)
-        if ctx.flat:
-            _dw_gemm(dxm, x, out=_flat(w).view(w.shape[0], -1))
+        dw = _dw_gemm(dxm, x, out=_grad_dst(w, flat))
+        if flat:
             _grad_ready(w, b)
-            return dx, dres, None, None, None
-        dw = _dw_gemm(dxm, x)
-        return dx, dres, dw, db, dg, dbt, None, None
-
-
-class _LinearDropLNFlatFn(torch.autograd.Function):
-    """Same, parameters [w, b, gamma, beta] hidden from autograd; their
-    gradients land in the flat buffer."""
-
-    @staticmethod
-    def forward(ctx, x, res, params, p, eps):
-        y = _LinearDropLNFn.forward(ctx, x, res, *params, p, eps)
-        ctx.flat = True
-        return y
-
-    backward = staticmethod(_LinearDropLNFn.backward)
-
-
-def _dx_epilogue_ok(E, M, n_out, k):
-    """Whether the dX GEMM (M, n_out, k) would run on the gemm256 kernel —
-    the only one carrying the relu-mask / residual-add epilogues — through
-    the cached-W^T backend.  Opt-in, TFMX_FFN_BWD=fused (A/B arm, read per
-    call): with the aux tensor read in the epilogue's 2-byte store pattern
-    behind a 1-block/CU main loop, both fused GEMMs measured SLOWER than
-    GEMM + separate pass (docs/PERF.md), so the default stays split."""
-    return (os.environ.get("TFMX_FFN_BWD", "split") == "fused"
-            and _DX_BACKEND == "wt" and M >= 2048
-            and n_out % 64 == 0 and k % 64 == 0
-            and E.gemm256_viable(M, n_out, k))
+            dw = db = dg = dbt = None
+        return dx, dres, dw, db, dg, dbt, None, None, None
 
 
 class _FFNDropLNFn(torch.autograd.Function):
     """y = LN(dropout(relu(x @ W1^T + b1) @ W2^T + b2) + x)."""
 
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, gamma, beta, p, eps):
+    def forward(ctx, x, w1, b1, w2, b2, gamma, beta, hidden, p, eps):
         E = ext()
+        ctx.flat = hidden is not None
+        if ctx.flat:
+            w1, b1, w2, b2, gamma, beta = hidden
         h = _fwd_gemm(E, x, w1, b1, "relu")
         a = _fwd_gemm(E, h, w2, b2, None)
         y, s, mean, rstd, mask = _ln_drop_fwd(E, a, x, gamma, beta, eps, p)
         ctx.p = p
-        ctx.flat = False
         ctx.params = (w1, b1, w2, b2, gamma, beta)
         ctx.save_for_backward(x, h, s, mean, rstd, mask)
         return y
 
     @staticmethod
     def backward(ctx, dy):
+        # _grad_ready order (DDP overlap): (g, bt), then (w2, b2) before
+        # the dZ GEMM, then (w1, b1) before the final dX.
         E = ext()
         x, h, s, mean, rstd, mask = ctx.saved_tensors
         w1, b1, w2, b2, g, bt = ctx.params
         flat = ctx.flat
-        dres, dxm, dg, dbt, db2 = _ln_drop_bwd(E, ctx, dy, s, g, mean, rstd,
+        dres, dxm, dg, dbt, db2 = _ln_drop_bwd(E, ctx, dy, s, mean, rstd,
                                                mask, g, bt, b2)
-        dw2 = _dw_gemm(dxm, h, out=_flat(w2).view(w2.shape[0], -1)
-                       if flat else None)
+        dw2 = _dw_gemm(dxm, h, out=_grad_dst(w2, flat))
         if flat:
             _grad_ready(w2, b2)
         M, d, dff = x.shape[0], x.shape[1], h.shape[1]
@@ -693,34 +457,26 @@ class _FFNDropLNFn(torch.autograd.Function):
             dz = E.gemm256_nt(dxm, _wt_padded(E, w2), nob, 2, None, h)
         else:
             dz = E.relu_bwd(_dx_gemm(E, dxm, w2).contiguous(), h)
-        dw1 = _dw_gemm(dz, x, out=_flat(w1).view(w1.shape[0], -1)
-                       if flat else None)
+        dw1 = _dw_gemm(dz, x, out=_grad_dst(w1, flat))
         db1 = E.colsum(dz, _grad_dst(b1, flat)) if b1 is not None else None
         if flat:
             _grad_ready(w1, b1)
+            dw1 = db1 = dw2 = db2 = dg = dbt = None
         if _dx_epilogue_ok(E, M, d, dff):
             # dx = dz @ W1 + dres in one rounding
             dx = E.gemm256_nt(dz, _wt_padded(E, w1), nob, 3, None, dres)
         else:
             dx = _dx_gemm(E, dz, w1) + dres
-        if flat:
-            return dx, None, None, None
-        return dx, dw1, db1, dw2, db2, dg, dbt, None, None
-
-
-class _FFNDropLNFlatFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, params, p, eps):
-        y = _FFNDropLNFn.forward(ctx, x, *params, p, eps)
-        ctx.flat = True
-        return y
-
-    backward = staticmethod(_FFNDropLNFn.backward)
+        return dx, dw1, db1, dw2, db2, dg, dbt, None, None, None
 
 
 def _all_flat(*params):
     fl = [_flat(p) is not None for p in params if p is not None]
     return all(fl), any(fl)
+
+
+def _rows(t):
+    return t.reshape(-1, t.shape[-1]).contiguous()
 
 
 def linear_dropout_residual_layernorm(x, w, b, res, gamma, beta, rate: float,
@@ -733,14 +489,9 @@ def linear_dropout_residual_layernorm(x, w, b, res, gamma, beta, rate: float,
     if not (x.is_cuda and training and rate > 0.0 and allf == anyf):
         return dropout_residual_layernorm(linear(x, w, b), res, gamma, beta,
                                           rate, training, eps)
-    shp = res.shape
-    x2 = x.reshape(-1, x.shape[-1]).contiguous()
-    r2 = res.reshape(-1, shp[-1]).contiguous()
-    if allf:
-        y = _LinearDropLNFlatFn.apply(x2, r2, [w, b, gamma, beta], rate, eps)
-    else:
-        y = _LinearDropLNFn.apply(x2, r2, w, b, gamma, beta, rate, eps)
-    return y.view(shp)
+    y = _LinearDropLNFn.apply(_rows(x), _rows(res),
+                              *_slots(allf, w, b, gamma, beta), rate, eps)
+    return y.view(res.shape)
 
 
 def ffn_dropout_residual_layernorm(x, w1, b1, w2, b2, gamma, beta,
@@ -753,27 +504,21 @@ def ffn_dropout_residual_layernorm(x, w1, b1, w2, b2, gamma, beta,
         h = linear(x, w1, b1, activation="relu")
         return dropout_residual_layernorm(linear(h, w2, b2), x, gamma, beta,
                                           rate, training, eps)
-    shp = x.shape
-    x2 = x.reshape(-1, shp[-1]).contiguous()
-    if allf:
-        y = _FFNDropLNFlatFn.apply(x2, [w1, b1, w2, b2, gamma, beta], rate,
-                                   eps)
-    else:
-        y = _FFNDropLNFn.apply(x2, w1, b1, w2, b2, gamma, beta, rate, eps)
-    return y.view(shp)
+    y = _FFNDropLNFn.apply(_rows(x), *_slots(allf, w1, b1, w2, b2, gamma,
+                                             beta), rate, eps)
+    return y.view(x.shape)
+
+
+def _residual_ln_gpu(x, res, gamma, beta, rate, eps):
+    y = _ResidualLNFn.apply(_rows(x), _rows(res),
+                            *_slots(_flat(gamma) is not None, gamma, beta),
+                            rate, eps)
+    return y.view(x.shape)
 
 
 def residual_layernorm(x, res, gamma, beta, eps: float = 1e-6):
     if x.is_cuda:
-        shp = x.shape
-        d = shp[-1]
-        x2 = x.reshape(-1, d).contiguous()
-        r2 = res.reshape(-1, d).contiguous()
-        if _flat(gamma) is not None:
-            y = _ResidualLNFlatFn.apply(x2, r2, [gamma, beta], eps)
-        else:
-            y = _ResidualLNFn.apply(x2, r2, gamma, beta, eps)
-        return y.view(shp)
+        return _residual_ln_gpu(x, res, gamma, beta, 0.0, eps)
     if x.dtype in (torch.bfloat16, torch.float16):
         return R.residual_layernorm(x.float(), res.float(), gamma.float(),
                                     beta.float(), eps).to(x.dtype)
@@ -788,15 +533,7 @@ def dropout_residual_layernorm(x, res, gamma, beta, rate: float,
     if not training or rate == 0.0:
         return residual_layernorm(x, res, gamma, beta, eps)
     if x.is_cuda:
-        shp = x.shape
-        d = shp[-1]
-        x2 = x.reshape(-1, d).contiguous()
-        r2 = res.reshape(-1, d).contiguous()
-        if _flat(gamma) is not None:
-            y = _DropResidualLNFlatFn.apply(x2, r2, [gamma, beta], rate, eps)
-        else:
-            y = _DropResidualLNFn.apply(x2, r2, gamma, beta, rate, eps)
-        return y.view(shp)
+        return _residual_ln_gpu(x, res, gamma, beta, rate, eps)
     xd = torch.nn.functional.dropout(x, p=rate, training=True)
     return residual_layernorm(xd, res, gamma, beta, eps)
 
@@ -806,11 +543,19 @@ def dropout_residual_layernorm(x, res, gamma, beta, rate: float,
 # ---------------------------------------------------------------------------
 
 class _EmbedPEFn(torch.autograd.Function):
+    """Flat mode: the dW scatter-add casts straight into the flat view, and
+    the weight slot holds a dummy differentiable `marker` instead — the
+    output must still require grad (x flows onward), so something has to
+    thread the graph."""
+
     @staticmethod
-    def forward(ctx, tokens, weight, pe):
+    def forward(ctx, tokens, weight, hidden, pe):
         E = ext()
+        ctx.flat = hidden is not None
+        if ctx.flat:
+            (weight,) = hidden
         y = E.embed_pe_fwd(tokens, weight, pe)
-        ctx.vocab = weight.shape[0]
+        ctx.weight = weight
         ctx.save_for_backward(tokens)
         return y
 
@@ -818,34 +563,13 @@ class _EmbedPEFn(torch.autograd.Function):
     def backward(ctx, dy):
         E = ext()
         (tokens,) = ctx.saved_tensors
-        dw = E.embed_pe_bwd(dy.contiguous(), tokens, ctx.vocab)
-        return None, dw, None
-
-
-class _EmbedPEFlatFn(torch.autograd.Function):
-    """Embedding fwd with dW scatter-add cast straight into the flat view.
-    Output still requires grad (x flows onward), so a dummy differentiable
-    input threads the graph."""
-
-    @staticmethod
-    def forward(ctx, marker, tokens, wref, pe):
-        E = ext()
-        (weight,) = wref
-        y = E.embed_pe_fwd(tokens, weight, pe)
-        ctx.vocab = weight.shape[0]
-        ctx.wref = wref
-        ctx.save_for_backward(tokens)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        E = ext()
-        (tokens,) = ctx.saved_tensors
-        (weight,) = ctx.wref
-        E.embed_pe_bwd(dy.contiguous(), tokens, ctx.vocab,
-                       _flat(weight).view(-1))
-        _grad_ready(weight)
-        return None, None, None, None
+        weight = ctx.weight
+        dw = E.embed_pe_bwd(dy.contiguous(), tokens, weight.shape[0],
+                            _grad_dst(weight, ctx.flat))
+        if ctx.flat:
+            _grad_ready(weight)
+            dw = None
+        return None, dw, None, None
 
 
 def embedding_scale_pe_at(tokens, weight, pe, pos: int):
@@ -861,45 +585,21 @@ def embedding_scale_pe(tokens, weight, pe):
         if _flat(weight) is not None and torch.is_grad_enabled():
             marker = torch.empty(0, device=weight.device,
                                  dtype=weight.dtype, requires_grad=True)
-            return _EmbedPEFlatFn.apply(marker, tokens.contiguous(),
-                                        [weight], pe)
-        return _EmbedPEFn.apply(tokens.contiguous(), weight, pe)
+            return _EmbedPEFn.apply(tokens.contiguous(), marker, [weight], pe)
+        return _EmbedPEFn.apply(tokens.contiguous(), weight, None, pe)
     if weight.dtype in (torch.bfloat16, torch.float16):
         return R.embedding_scale_pe(tokens, weight.float(), pe[None].float()).to(weight.dtype)
     return R.embedding_scale_pe(tokens, weight, pe[None].to(weight.dtype))
 
 
 # ---------------------------------------------------------------------------
-# Dropout (K11): mask saved for exact backward; seeds from torch RNG.
+# Dropout (K11): mask saved for exact backward.
 # ---------------------------------------------------------------------------
-
-# HIP-graph capture support: while a step is being
-# captured, dropout seeds must come from a DEVICE counter (advanced
-# in-graph by the optimizer's adam_coefs kernel) — a host seed would be
-# baked into the graph and every replay would reuse the same mask.  Each
-# call site gets a distinct salt (capture-order is deterministic).
-_GRAPH_SEED_T = None
-_GRAPH_SALT = [0]
-
-
-def set_graph_rng(seed_tensor):
-    """Install (or clear, with None) the device seed tensor used by dropout
-    during graph capture."""
-    global _GRAPH_SEED_T
-    _GRAPH_SEED_T = seed_tensor
-    _GRAPH_SALT[0] = 0
-
 
 class _DropoutFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, p):
-        E = ext()
-        if _GRAPH_SEED_T is not None:
-            _GRAPH_SALT[0] += 1
-            y, mask = E.dropout_fwd(x, p, _GRAPH_SALT[0], _GRAPH_SEED_T)
-        else:
-            seed = int(torch.randint(0, 2**31 - 1, (1,)).item())
-            y, mask = E.dropout_fwd(x, p, seed)
+        y, mask = ext().dropout_fwd(x, p, *_dropout_seed())
         ctx.p = p
         ctx.save_for_backward(mask)
         return y
@@ -986,7 +686,6 @@ def masked_accuracy_counts(logits, targets):
     SparseCategoricalAccuracy semantics, train.py:72-73) instead of a
     mean of batch-means."""
     if logits.is_cuda:
-        B = logits.shape
         V = logits.shape[-1]
         correct, total = ext().accuracy(logits.reshape(-1, V).contiguous(),
                                         targets.reshape(-1).contiguous())
