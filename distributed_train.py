@@ -36,7 +36,7 @@ def main(epochs, enable_function, buffer_size, batch_size, sequence_length,
          seed=1234, log_interval=100, eval_steps=50, synthetic_data=False,
          synthetic_vocab=32768, steps_per_epoch=100, max_decode_len=10,
          debug_sync=False, clip_grad_norm=0.0, skip_nonfinite_grads=False,
-         **_ignored):
+         grad_accum_steps=1, **_ignored):
     if debug_sync:  # race/fault localization mode
         os.environ["AMD_SERIALIZE_KERNEL"] = "3"
         os.environ["HIP_LAUNCH_BLOCKING"] = "1"
@@ -89,7 +89,8 @@ def main(epochs, enable_function, buffer_size, batch_size, sequence_length,
         device=device, log_interval=log_interval, eval_steps=eval_steps,
         max_decode_len=max_decode_len, is_rank0=(rank == 0),
         clip_grad_norm=clip_grad_norm,
-        skip_nonfinite_grads=skip_nonfinite_grads)
+        skip_nonfinite_grads=skip_nonfinite_grads,
+        grad_accum_steps=grad_accum_steps)
     train.load_ckpt()
     train.training_loop(train_ds, test_ds)
     if rank == 0:

@@ -59,7 +59,7 @@ def main(epochs, enable_function, buffer_size, batch_size, sequence_length,
          seed=1234, log_interval=100, eval_steps=50, synthetic_data=False,
          synthetic_vocab=32768, steps_per_epoch=100, max_decode_len=10,
          trace_dir=None, debug_sync=False, clip_grad_norm=0.0,
-         skip_nonfinite_grads=False, **_ignored):
+         skip_nonfinite_grads=False, grad_accum_steps=1, **_ignored):
     if debug_sync:
         # race/fault localization: every kernel launch is
         # serialized and synchronous so a fault is attributed to the
@@ -102,7 +102,8 @@ def main(epochs, enable_function, buffer_size, batch_size, sequence_length,
                   log_interval=log_interval, eval_steps=eval_steps,
                   max_decode_len=max_decode_len,
                   clip_grad_norm=clip_grad_norm,
-                  skip_nonfinite_grads=skip_nonfinite_grads)
+                  skip_nonfinite_grads=skip_nonfinite_grads,
+                  grad_accum_steps=grad_accum_steps)
     train.load_ckpt()
     train.install_signal_handler()  # SIGTERM/SIGINT -> checkpoint + exit
     if trace_dir:

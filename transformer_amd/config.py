@@ -98,6 +98,11 @@ def transformer_flags(parser: argparse.ArgumentParser | None = None) -> argparse
                         help="clip gradients to this global L2 norm; 0 = off")
     _add_bool_flag(parser, "skip_nonfinite_grads", False,
                    "skip optimizer steps whose gradient norm is not finite")
+    parser.add_argument("--grad_accum_steps", type=int, default=1,
+                        help="micro-batches per optimizer step: each batch is "
+                             "split along dim 0 and the gradients are summed "
+                             "in fp32; --batch_size stays the global batch "
+                             "per optimizer step; 1 = off")
     return parser
 
 
@@ -136,6 +141,7 @@ def flags_dict(args: argparse.Namespace) -> dict:
         "debug_sync": args.debug_sync,
         "clip_grad_norm": args.clip_grad_norm,
         "skip_nonfinite_grads": args.skip_nonfinite_grads,
+        "grad_accum_steps": args.grad_accum_steps,
     }
 
 

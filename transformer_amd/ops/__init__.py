@@ -62,5 +62,6 @@ from .functional import (  # noqa: E402
     masked_cross_entropy,
     masked_accuracy,
     masked_accuracy_counts,
+    masked_accuracy_counts_t,
     argmax_lastdim,
 )

@@ -305,3 +305,162 @@ void adam_fused_dev_clip(torch::Tensor master, torch::Tensor m,
       coefs.data_ptr<float>(), (float)beta1, (float)beta2, (float)eps,
       stats.data_ptr<float>());
 }
+
+// ---- accumulator-reading variants (gradient accumulation) -----------------
+// The gradient is the fp32 accumulator filled by grad_accum (grad_accum.hip)
+// instead of the bf16 flat gradient.  Same adam_elem body, so with the
+// accumulator holding bf16-representable values and a 4-aligned length the
+// update is bit-identical to the bf16-gradient kernels above.  Every thread
+// also stores ZEROS back over the accumulator elements it read: that restores
+// the "all-zero between optimizer steps" invariant grad_accum relies on, for
+// +4 B/param in a pass that already reads the buffer.  `stats` may be null
+// (scale 1, never vetoed).  On a vetoed step (stats[2] != 0) master/m/v/param
+// are not touched but the accumulator is still zeroed — a poisoned sum must
+// not leak into the next step.
+DEV_INLINE void adam_acc_update(float* __restrict__ master,
+                                float* __restrict__ m, float* __restrict__ v,
+                                float* __restrict__ acc,
+                                short* __restrict__ param, long n, float lr,
+                                float b1, float b2, float eps, float bc1,
+                                float bc2, const float* __restrict__ stats) {
+  const bool veto = stats != nullptr && stats[2] != 0.f;
+  const float gscale = (stats != nullptr && !veto) ? stats[1] : 1.0f;
+  const long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (i + 4 <= n) {
+    if (!veto) {
+      f32x4 mm = *(const f32x4*)(m + i);
+      f32x4 vv = *(const f32x4*)(v + i);
+      f32x4 ww = *(const f32x4*)(master + i);
+      f32x4 g4 = *(const f32x4*)(acc + i);
+      s16x4 p4;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float mj = mm[j], vj = vv[j];
+        float w = adam_elem(g4[j] * gscale, mj, vj, ww[j], lr, b1, b2, eps,
+                            bc1, bc2);
+        mm[j] = mj;
+        vv[j] = vj;
+        ww[j] = w;
+        p4[j] = f2bfbits(w);
+      }
+      *(f32x4*)(m + i) = mm;
+      *(f32x4*)(v + i) = vv;
+      *(f32x4*)(master + i) = ww;
+      *(s16x4*)(param + i) = p4;
+    }
+    f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    *(f32x4*)(acc + i) = z;
+  } else {
+    for (long j = i; j < n; ++j) {
+      if (!veto) {
+        float mj = m[j], vj = v[j];
+        float w = adam_elem(acc[j] * gscale, mj, vj, master[j], lr, b1, b2,
+                            eps, bc1, bc2);
+        m[j] = mj;
+        v[j] = vj;
+        master[j] = w;
+        param[j] = f2bfbits(w);
+      }
+      acc[j] = 0.f;
+    }
+  }
+}
+
+__global__ void adam_acc_kernel(float* __restrict__ master,
+                                float* __restrict__ m, float* __restrict__ v,
+                                float* __restrict__ acc,
+                                short* __restrict__ param, long n, float lr,
+                                float b1, float b2, float eps, float bc1,
+                                float bc2, const float* __restrict__ stats) {
+  adam_acc_update(master, m, v, acc, param, n, lr, b1, b2, eps, bc1, bc2,
+                  stats);
+}
+
+__global__ void adam_dev_acc_kernel(float* __restrict__ master,
+                                    float* __restrict__ m,
+                                    float* __restrict__ v,
+                                    float* __restrict__ acc,
+                                    short* __restrict__ param, long n,
+                                    const float* __restrict__ coefs, float b1,
+                                    float b2, float eps,
+                                    const float* __restrict__ stats) {
+  adam_acc_update(master, m, v, acc, param, n, coefs[0], b1, b2, eps,
+                  coefs[1], coefs[2], stats);
+}
+
+static const float* check_acc_args(const torch::Tensor& master,
+                                   const torch::Tensor& m,
+                                   const torch::Tensor& v,
+                                   const torch::Tensor& acc,
+                                   const torch::Tensor& param,
+                                   const c10::optional<torch::Tensor>& stats) {
+  TORCH_CHECK(master.is_cuda() && master.dtype() == torch::kFloat32 &&
+              master.is_contiguous());
+  TORCH_CHECK(m.is_cuda() && m.dtype() == torch::kFloat32 &&
+              m.is_contiguous() && v.is_cuda() &&
+              v.dtype() == torch::kFloat32 && v.is_contiguous());
+  TORCH_CHECK(acc.is_cuda() && acc.dtype() == torch::kFloat32 &&
+              acc.is_contiguous());
+  TORCH_CHECK(param.is_cuda() && param.dtype() == torch::kBFloat16 &&
+              param.is_contiguous());
+  const long n = master.numel();
+  TORCH_CHECK(m.numel() == n && v.numel() == n && acc.numel() == n &&
+              param.numel() == n);
+  // the vector path reads f32x4 / s16x4 at the bases
+  TORCH_CHECK(((size_t)master.data_ptr() & 15) == 0 &&
+              ((size_t)m.data_ptr() & 15) == 0 &&
+              ((size_t)v.data_ptr() & 15) == 0 &&
+              ((size_t)acc.data_ptr() & 15) == 0 &&
+              ((size_t)param.data_ptr() & 7) == 0,
+              "adam_fused_acc: buffers must be 16-byte aligned");
+  TORCH_CHECK(acc.get_device() == master.get_device() &&
+              param.get_device() == master.get_device());
+  if (!stats.has_value()) return nullptr;
+  const torch::Tensor& st = *stats;
+  TORCH_CHECK(st.is_cuda() && st.dtype() == torch::kFloat32 &&
+              st.is_contiguous() && st.numel() >= 4 &&
+              st.get_device() == master.get_device());
+  return st.data_ptr<float>();
+}
+
+// adam_fused with the fp32 accumulator as the gradient; the accumulator is
+// all-zero afterwards.  `stats` (optional) as in adam_fused_clip.
+void adam_fused_acc(torch::Tensor master, torch::Tensor m, torch::Tensor v,
+                    torch::Tensor acc, torch::Tensor param, double lr,
+                    double beta1, double beta2, double eps, int64_t step,
+                    c10::optional<torch::Tensor> stats) {
+  const float* st = check_acc_args(master, m, v, acc, param, stats);
+  long n = master.numel();
+  float bc1 = 1.0f / (1.0f - powf((float)beta1, (float)step));
+  float bc2 = 1.0f / (1.0f - powf((float)beta2, (float)step));
+  auto stream = at::hip::getCurrentHIPStream();
+  adam_acc_kernel<<<((n + 3) / 4 + 255) / 256, 256, 0, stream>>>(
+      master.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
+      acc.data_ptr<float>(), (short*)param.data_ptr(), n, (float)lr,
+      (float)beta1, (float)beta2, (float)eps, bc1, bc2, st);
+}
+
+// Graph-capturable form: device step tensor + in-kernel Noam lr, as
+// adam_fused_dev(_clip).  The step tensor advances on a vetoed step too.
+void adam_fused_dev_acc(torch::Tensor master, torch::Tensor m,
+                        torch::Tensor v, torch::Tensor acc,
+                        torch::Tensor param, torch::Tensor step,
+                        torch::Tensor coefs, double d_model, double warmup,
+                        double beta1, double beta2, double eps,
+                        c10::optional<torch::Tensor> stats) {
+  const float* st = check_acc_args(master, m, v, acc, param, stats);
+  TORCH_CHECK(step.dtype() == torch::kInt64 && step.numel() == 1 &&
+              step.is_cuda());
+  TORCH_CHECK(coefs.dtype() == torch::kFloat32 && coefs.numel() >= 3 &&
+              coefs.is_cuda());
+  long n = master.numel();
+  auto stream = at::hip::getCurrentHIPStream();
+  adam_coefs_kernel<<<1, 1, 0, stream>>>(
+      (long long*)step.data_ptr(), coefs.data_ptr<float>(),
+      1.0f / sqrtf((float)d_model),
+      powf((float)warmup, -1.5f), (float)beta1, (float)beta2);
+  adam_dev_acc_kernel<<<((n + 3) / 4 + 255) / 256, 256, 0, stream>>>(
+      master.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
+      acc.data_ptr<float>(), (short*)param.data_ptr(), n,
+      coefs.data_ptr<float>(), (float)beta1, (float)beta2, (float)eps, st);
+}

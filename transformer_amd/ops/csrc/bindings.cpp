@@ -105,7 +105,22 @@ void adam_fused_dev_clip(torch::Tensor master, torch::Tensor m,
 void grad_norm_clip(torch::Tensor grad, torch::Tensor partials,
                     torch::Tensor stats, double max_norm,
                     bool skip_nonfinite);
+void grad_norm_clip_f32(torch::Tensor acc, torch::Tensor partials,
+                        torch::Tensor stats, double max_norm,
+                        bool skip_nonfinite);
 int64_t grad_norm_blocks(int64_t n);
+void grad_accum(torch::Tensor grad, torch::Tensor acc);
+int64_t grad_accum_max_blocks();
+void adam_fused_acc(torch::Tensor master, torch::Tensor m, torch::Tensor v,
+                    torch::Tensor acc, torch::Tensor param, double lr,
+                    double beta1, double beta2, double eps, int64_t step,
+                    c10::optional<torch::Tensor> stats);
+void adam_fused_dev_acc(torch::Tensor master, torch::Tensor m,
+                        torch::Tensor v, torch::Tensor acc,
+                        torch::Tensor param, torch::Tensor step,
+                        torch::Tensor coefs, double d_model, double warmup,
+                        double beta1, double beta2, double eps,
+                        c10::optional<torch::Tensor> stats);
 int64_t grad_norm_max_blocks();
 
 torch::Tensor argmax_lastdim(torch::Tensor logits);
@@ -219,6 +234,30 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("grad_norm_blocks", &grad_norm_blocks,
         "stage-1 block count (= workspace elements) for a length-n input");
   m.def("grad_norm_max_blocks", &grad_norm_max_blocks);
+  m.def("grad_norm_clip_f32", &grad_norm_clip_f32,
+        "grad_norm_clip over a 1-D fp32 tensor (the gradient accumulator)",
+        pybind11::arg("acc"), pybind11::arg("partials"),
+        pybind11::arg("stats"), pybind11::arg("max_norm"),
+        pybind11::arg("skip_nonfinite"));
+  m.def("grad_accum", &grad_accum,
+        "acc (fp32) += grad (bf16), 1-D, same length; any base alignment",
+        pybind11::arg("grad"), pybind11::arg("acc"));
+  m.def("grad_accum_max_blocks", &grad_accum_max_blocks);
+  m.def("adam_fused_acc", &adam_fused_acc,
+        "adam_fused reading the fp32 accumulator, which it zeroes; optional "
+        "stats = {norm, scale, skipped, total} scales / vetoes the update",
+        pybind11::arg("master"), pybind11::arg("m"), pybind11::arg("v"),
+        pybind11::arg("acc"), pybind11::arg("param"), pybind11::arg("lr"),
+        pybind11::arg("beta1"), pybind11::arg("beta2"), pybind11::arg("eps"),
+        pybind11::arg("step"), pybind11::arg("stats") = pybind11::none());
+  m.def("adam_fused_dev_acc", &adam_fused_dev_acc,
+        "adam_fused_dev reading the fp32 accumulator, which it zeroes",
+        pybind11::arg("master"), pybind11::arg("m"), pybind11::arg("v"),
+        pybind11::arg("acc"), pybind11::arg("param"), pybind11::arg("step"),
+        pybind11::arg("coefs"), pybind11::arg("d_model"),
+        pybind11::arg("warmup"), pybind11::arg("beta1"),
+        pybind11::arg("beta2"), pybind11::arg("eps"),
+        pybind11::arg("stats") = pybind11::none());
   m.def("argmax_lastdim", &argmax_lastdim);
   m.def("accuracy", &accuracy);
 }

@@ -79,6 +79,59 @@ void grad_sumsq_kernel(const short* __restrict__ g, long n,
     partials[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
 }
 
+// Stage 1 for the fp32 gradient accumulator (grad_accum.hip).  Same split,
+// same 8 elements per thread per trip (two f32x4 loads), same per-lane
+// accumulators and the same combine tree as grad_sumsq_kernel, launched on
+// the same gn_blocks(n) grid, so the workspace size, the add-chain length
+// and the "result bits depend on n alone" property carry over.  The head is
+// < 4 elements (up to the first 16-byte boundary of a 4-byte-aligned base).
+__global__ __launch_bounds__(GN_THREADS)
+void grad_sumsq_f32_kernel(const float* __restrict__ g, long n,
+                           float* __restrict__ partials) {
+  long head = (long)(((16 - ((size_t)g & 15)) & 15) >> 2);
+  if (head > n) head = n;
+  const long nvec = (n - head) / GN_VEC;
+  const long tail0 = head + nvec * GN_VEC;
+  const f32x4* __restrict__ body = (const f32x4*)(g + head);
+
+  float acc[GN_VEC];
+#pragma unroll
+  for (int j = 0; j < GN_VEC; ++j) acc[j] = 0.f;
+
+  const long stride = (long)gridDim.x * GN_THREADS;
+#pragma unroll 4
+  for (long i = (long)blockIdx.x * GN_THREADS + threadIdx.x; i < nvec;
+       i += stride) {
+    f32x4 x0 = body[2 * i];
+    f32x4 x1 = body[2 * i + 1];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      acc[j] += x0[j] * x0[j];
+      acc[4 + j] += x1[j] * x1[j];
+    }
+  }
+  if (blockIdx.x == 0) {
+    const long t = threadIdx.x;
+    if (t < head) {
+      float f = g[t];
+      acc[0] += f * f;
+    }
+    if (tail0 + t < n && t < GN_VEC) {
+      float f = g[tail0 + t];
+      acc[1] += f * f;
+    }
+  }
+  float s = ((acc[0] + acc[1]) + (acc[2] + acc[3])) +
+            ((acc[4] + acc[5]) + (acc[6] + acc[7]));
+  s = wave_sum(s);
+
+  __shared__ float wsum[GN_THREADS / WAVE];
+  if ((threadIdx.x & (WAVE - 1)) == 0) wsum[threadIdx.x / WAVE] = s;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    partials[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+
 // Stage 2: one block.  Thread t sums partials t, t+256, ... in double, then a
 // fixed LDS tree combines the 256 doubles.  Thread 0 applies the rules:
 //   scale = 1.0f exactly          when max_norm <= 0 or norm <= max_norm
@@ -145,6 +198,32 @@ void grad_norm_clip(torch::Tensor grad, torch::Tensor partials,
   auto stream = at::hip::getCurrentHIPStream();
   grad_sumsq_kernel<<<nb, GN_THREADS, 0, stream>>>(
       (const short*)grad.data_ptr(), n, partials.data_ptr<float>());
+  grad_norm_finalize_kernel<<<1, GN_THREADS, 0, stream>>>(
+      partials.data_ptr<float>(), nb, (float)max_norm,
+      skip_nonfinite ? 1 : 0, stats.data_ptr<float>());
+}
+
+// grad_norm_clip for the fp32 gradient accumulator: fp32 stage 1, the same
+// finalize, hence the same stats layout and rules.  The base of `acc` need
+// only be 4-byte aligned.
+void grad_norm_clip_f32(torch::Tensor acc, torch::Tensor partials,
+                        torch::Tensor stats, double max_norm,
+                        bool skip_nonfinite) {
+  TORCH_CHECK(acc.is_cuda() && acc.dtype() == torch::kFloat32 &&
+              acc.dim() == 1 && acc.is_contiguous() && acc.numel() >= 1);
+  TORCH_CHECK(partials.is_cuda() && partials.dtype() == torch::kFloat32 &&
+              partials.is_contiguous());
+  TORCH_CHECK(stats.is_cuda() && stats.dtype() == torch::kFloat32 &&
+              stats.is_contiguous() && stats.numel() >= 4);
+  TORCH_CHECK(partials.get_device() == acc.get_device() &&
+              stats.get_device() == acc.get_device());
+  const long n = acc.numel();
+  const int nb = gn_blocks(n);
+  TORCH_CHECK(partials.numel() >= nb, "grad_norm_clip_f32: workspace holds ",
+              partials.numel(), " partials, need ", nb);
+  auto stream = at::hip::getCurrentHIPStream();
+  grad_sumsq_f32_kernel<<<nb, GN_THREADS, 0, stream>>>(
+      acc.data_ptr<float>(), n, partials.data_ptr<float>());
   grad_norm_finalize_kernel<<<1, GN_THREADS, 0, stream>>>(
       partials.data_ptr<float>(), nb, (float)max_norm,
       skip_nonfinite ? 1 : 0, stats.data_ptr<float>());

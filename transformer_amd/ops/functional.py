@@ -25,6 +25,7 @@ from . import ext
 from .gemm_dispatch import (  # noqa: F401  (re-exported: graph.py, optimizer,
     bump_weight_version,      # models and tests reach for them here)
     prepare_weight_caches,
+    refresh_weight_caches,
     set_capture_hint,
     _dense2d,
     _dw_db_gemm,
@@ -693,3 +694,14 @@ def masked_accuracy_counts(logits, targets):
     pred = logits.argmax(dim=-1)
     mask = targets != 0
     return (float(((pred == targets) & mask).sum()), float(mask.sum()))
+
+
+def masked_accuracy_counts_t(logits, targets):
+    """[correct, total] as a float64 tensor on the logits' device, with NO
+    host synchronisation (masked_accuracy_counts copies its two counters to
+    the host on every call).  For callers that sum the counts of several
+    micro-batches, or record them in a captured graph, and read them once."""
+    pred = argmax_lastdim(logits)
+    mask = targets != 0
+    return torch.stack([((pred == targets) & mask).sum(),
+                        mask.sum()]).to(torch.float64)

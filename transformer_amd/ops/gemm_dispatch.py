@@ -60,6 +60,22 @@ class _WeightTransposeCache:
             dev = next(iter(self.entries.values()))[1].device
             self.table = self._build_table(dev)
 
+    def refresh(self, E):
+        """Relaunch transpose_batch NOW and mark every entry current,
+        instead of waiting for the first stale lookup.  A captured
+        optimizer-apply graph records this right after its Adam kernel, so
+        the micro-batch graphs replayed after it find fresh transposes and
+        record no refresh of their own.  The table must exist already when
+        this runs under capture (prepare())."""
+        if not self.entries:
+            return
+        if self.table is None:
+            dev = next(iter(self.entries.values()))[1].device
+            self.table = self._build_table(dev)
+        E.transpose_batch(self.table)
+        for e in self.entries.values():
+            e[0] = self.version
+
     def get(self, E, w, gran=64):
         """W[N,K]^T in a (K, Np) buffer, Np = N rounded up to `gran` (pad
         columns zero) — the NT B-operand for dX.  gran=256 matches
@@ -98,6 +114,12 @@ def prepare_weight_caches():
     host->device copy, which is illegal inside hipGraph capture) — called
     by CapturedTrainStep between warmup and capture."""
     _WT_CACHE.prepare()
+
+
+def refresh_weight_caches():
+    """Refresh every cached transpose eagerly (see
+    _WeightTransposeCache.refresh)."""
+    _WT_CACHE.refresh(ext())
 
 
 # GEMM backend (round 2): every training-shape GEMM runs hand-written.

@@ -15,6 +15,14 @@ Gradient averaging semantics follow the reference: the
 loss is pre-scaled by 1/global_batch on every replica, so a SUM all-reduce
 yields the exact global-batch gradient — no extra division.
 
+Gradient accumulation (NoamAdam accum_steps > 1): the gradient is complete
+only after the LAST micro backward, so the readiness callbacks are muted
+(`set_accumulate(True)`) and `finalize_accum(acc)` all-reduces the fp32
+accumulator over the same bucket slices once per optimizer step.  Backward
+overlap is given up on this path; the wire volume is 4 B/param once instead
+of 2 B/param N times.  The clip/skip decision then runs on the reduced
+accumulator, so ranks still agree.  N=1 keeps the callback path untouched.
+
 Not stock DistributedDataParallel: the bucket manager is ours, built on
 post-accumulate-grad hooks + async process-group collectives.
 """
@@ -103,7 +111,10 @@ class BucketedDataParallel:
         _F.set_grad_ready_callback(flat.params, self._on_param_ready)
         # launch-origin accounting (overlap evidence: callback launches
         # happen DURING backward, finalize launches are stragglers)
-        self.stats = {"callback": 0, "finalize": 0}
+        self.stats = {"callback": 0, "finalize": 0, "accum": 0}
+        # True while micro-batches are being accumulated: readiness
+        # callbacks launch nothing, finalize_accum() does all the work
+        self.accumulating = False
         self._reset_step()
 
     def detach(self):
@@ -115,8 +126,14 @@ class BucketedDataParallel:
             h.remove()
         self._hooks = []
 
+    def set_accumulate(self, on: bool):
+        """Mute (True) or restore (False) the per-bucket launches from the
+        readiness callbacks.  While muted, use finalize_accum()."""
+        self.accumulating = bool(on)
+        self._reset_step()
+
     def _on_param_ready(self, p):
-        if not self.active:
+        if not self.active or self.accumulating:
             return
         bi = self._param_bucket.get(id(p))
         if bi is None:
@@ -147,7 +164,7 @@ class BucketedDataParallel:
         bi = self._param_bucket[id(p)]
 
         def hook(_param):
-            if not self.active:
+            if not self.active or self.accumulating:
                 return
             b = self.buckets[bi]
             b["pending"] -= 1
@@ -166,10 +183,32 @@ class BucketedDataParallel:
         if self.world > 1:
             dist.broadcast(self.flat.flat_w, src=0, group=self.pg)
 
+    def finalize_accum(self, acc: torch.Tensor):
+        """Call after the last micro backward + accumulate(), before
+        optimizer.step(): async SUM all-reduces of the fp32 accumulator
+        `acc` (flat, flat.numel elements) over the bucket slices, then wait
+        for all of them.  One launch per bucket per optimizer step."""
+        if not self.active:
+            return
+        if acc.numel() != self.flat.numel:
+            raise ValueError("accumulator does not match the flat buffer")
+        works = []
+        for b in self.buckets:
+            self.stats["accum"] += 1
+            works.append(dist.all_reduce(acc[b["lo"]:b["hi"]],
+                                         op=dist.ReduceOp.SUM, group=self.pg,
+                                         async_op=True))
+        for w in works:
+            w.wait()
+
     def finalize(self):
         """Call after loss.backward(), before optimizer.step()."""
         if not self.active:
             return
+        if self.accumulating:
+            raise RuntimeError("finalize() while accumulating: the bf16 "
+                               "buffer holds one micro-gradient only; use "
+                               "finalize_accum(acc)")
         for b in self.buckets:
             if b["work"] is None and b["pending"] > 0:
                 # params that produced no grad this step (robustness)

@@ -18,6 +18,16 @@ clipped Adam kernels), so a hipGraph-captured step can veto itself without
 a host sync.  flat_g's alignment padding is always zero, so one reduction
 over the buffer is the exact global norm; it is also the buffer the DP
 runtime all-reduces, so every rank takes the same decision.
+
+Optional gradient accumulation (accum_steps > 1, off by default): every
+backward kernel OVERWRITES its slice of flat_g, so "backward N times, then
+step" needs a second buffer.  accumulate() adds the bf16 micro-gradient into
+one fp32 accumulator of flat.numel (grad_accum.hip); step() and
+step_captured() then take the norm pass and the Adam update from that
+accumulator, and the Adam kernel stores zeros back into it as it goes, so
+the accumulator is all-zero between optimizer steps and needs no "first
+micro-step" case anywhere.  With accum_steps == 1 nothing is allocated and
+exactly the bf16-gradient kernels are launched.
 """
 
 from __future__ import annotations
@@ -108,12 +118,21 @@ class NoamAdam:
     the weights stay untouched, `skipped_steps` grows by one, and
     `step_count` (hence the Noam schedule) still advances.  With both off
     (the default) step()/step_captured() launch exactly the unguarded
-    kernels."""
+    kernels.
+
+    accum_steps > 1 switches the gradient source to an fp32 accumulator:
+    call accumulate() after each micro backward, then step() once.  The
+    guard then judges the accumulated gradient.  The accumulator(s) are
+    all-zero after every step(), skipped or not."""
 
     def __init__(self, model: torch.nn.Module, d_model: int,
                  warmup_steps: int = 60000, betas=(0.9, 0.98), eps: float = 1e-9,
                  use_flat: bool | None = None, max_grad_norm: float = 0.0,
-                 skip_nonfinite: bool = False):
+                 skip_nonfinite: bool = False, accum_steps: int = 1):
+        if int(accum_steps) < 1:
+            raise ValueError(f"accum_steps must be >= 1, got {accum_steps}")
+        self.accum_steps = int(accum_steps)
+        self.acc = None         # flat fp32 accumulator (accum_steps > 1)
         self.schedule = NoamSchedule(d_model, warmup_steps)
         self.betas, self.eps = betas, eps
         self.step_count = 0
@@ -148,6 +167,15 @@ class NoamAdam:
                 ext().grad_norm_blocks(self.flat.numel), dtype=torch.float32,
                 device=dev)
             self._gn_stats = torch.zeros(4, dtype=torch.float32, device=dev)
+        if self.accum_steps > 1:
+            # allocated once, never inside a capture
+            if self.flat is not None:
+                self.acc = torch.zeros(self.flat.numel, dtype=torch.float32,
+                                       device=self.flat.flat_g.device)
+            else:
+                for p, st in zip(self.params, self.state):
+                    st["acc"] = torch.zeros_like(p, dtype=torch.float32)
+                    st["acc_live"] = False
 
     # ---- gradient guard ---------------------------------------------------
     def last_grad_norm(self) -> float:
@@ -168,8 +196,48 @@ class NoamAdam:
         return self._skipped
 
     def _device_norm_pass(self):
+        if self.acc is not None:
+            ext().grad_norm_clip_f32(self.acc, self._gn_ws, self._gn_stats,
+                                     self.max_grad_norm, self.skip_nonfinite)
+            return
         ext().grad_norm_clip(self.flat.flat_g, self._gn_ws, self._gn_stats,
                              self.max_grad_norm, self.skip_nonfinite)
+
+    # ---- gradient accumulation -------------------------------------------
+    def _need_accum(self):
+        if self.accum_steps <= 1:
+            raise RuntimeError(
+                "gradient accumulation is off: construct NoamAdam with "
+                "accum_steps > 1")
+
+    @torch.no_grad()
+    def accumulate(self):
+        """Add the gradient of the micro backward that just finished into
+        the fp32 accumulator(s).  Graph-capturable on the GPU flat path."""
+        self._need_accum()
+        if self.flat is not None:
+            self.flat.check()
+            if self.is_cuda:
+                ext().grad_accum(self.flat.flat_g, self.acc)
+            else:
+                self.acc.add_(self.flat.flat_g.float())
+            return
+        for p, st in zip(self.params, self.state):
+            if p.grad is not None:
+                st["acc"].add_(p.grad.float())
+                st["acc_live"] = True
+
+    @torch.no_grad()
+    def discard_accum(self):
+        """Zero the accumulator(s): drop the micro-gradients of an aborted
+        optimizer step."""
+        self._need_accum()
+        if self.flat is not None:
+            self.acc.zero_()
+            return
+        for st in self.state:
+            st["acc"].zero_()
+            st["acc_live"] = False
 
     def _host_guard(self, grads):
         """CPU semantics of the device guard: (skip, scale)."""
@@ -213,6 +281,16 @@ class NoamAdam:
         st, cf = self.graph_state()
         b1, b2 = self.betas
         self.flat.check()
+        if self.acc is not None:
+            # accumulated gradient: fp32 norm pass (if guarded), then the
+            # accumulator-reading update, which re-zeroes the accumulator
+            if self.guarded:
+                self._device_norm_pass()
+            _ext_fn().adam_fused_dev_acc(
+                self.master, self.m, self.v, self.acc, self.flat.flat_w, st,
+                cf, self.schedule.d_model, self.schedule.warmup_steps, b1,
+                b2, self.eps, self._gn_stats)
+            return
         if self.guarded:
             self._device_norm_pass()
             _ext_fn().adam_fused_dev_clip(
@@ -241,6 +319,8 @@ class NoamAdam:
         self.step_count += 1
         lr = self.schedule(self.step_count)
         b1, b2 = self.betas
+        if self.accum_steps > 1:
+            return self._accum_step(lr, b1, b2)
         if self.guarded:
             return self._guarded_step(lr, b1, b2)
         if self.flat is not None:
@@ -297,6 +377,38 @@ class NoamAdam:
                                   self.step_count, lr, b1, b2, self.eps)
             p.data.copy_(st["master"].to(p.dtype))
 
+    def _accum_step(self, lr, b1, b2):
+        """step() from the fp32 accumulator(s); leaves them all-zero."""
+        if self.flat is not None:
+            if self.is_cuda:
+                if self.guarded:
+                    self._device_norm_pass()
+                ext().adam_fused_acc(self.master, self.m, self.v, self.acc,
+                                     self.flat.flat_w, lr, b1, b2, self.eps,
+                                     self.step_count, self._gn_stats)
+                return
+            skip, scale = (self._host_guard([self.acc]) if self.guarded
+                           else (False, 1.0))
+            if not skip:
+                g = self.acc if scale == 1.0 else self.acc * scale
+                R.adam_step_reference(self.master, g, self.m, self.v,
+                                      self.step_count, lr, b1, b2, self.eps)
+                self.flat.flat_w.copy_(self.master.to(self.flat.flat_w.dtype))
+            self.acc.zero_()
+            return
+        live = [(p, st) for p, st in zip(self.params, self.state)
+                if st["acc_live"]]
+        skip, scale = (self._host_guard([st["acc"] for _, st in live])
+                       if self.guarded else (False, 1.0))
+        for p, st in live:
+            if not skip:
+                g = st["acc"] if scale == 1.0 else st["acc"] * scale
+                R.adam_step_reference(st["master"], g, st["m"], st["v"],
+                                      self.step_count, lr, b1, b2, self.eps)
+                p.data.copy_(st["master"].to(p.dtype))
+            st["acc"].zero_()
+            st["acc_live"] = False
+
     # -- checkpointing (C16) ------------------------------------------------
     def state_dict(self):
         d = {"step": self.step_count,
@@ -306,7 +418,8 @@ class NoamAdam:
         if self.flat is not None:
             d.update(master=self.master, m=self.m, v=self.v)
         else:
-            d.update(state=[{k: v for k, v in st.items()} for st in self.state])
+            d.update(state=[{k: st[k] for k in ("m", "v", "master")}
+                            for st in self.state])
         return d
 
     def load_state_dict(self, d):

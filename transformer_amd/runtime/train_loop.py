@@ -31,13 +31,18 @@ class Train:
                  max_decode_len: int = 10, is_rank0: bool = True,
                  use_flat: bool | None = None,
                  clip_grad_norm: float = 0.0,
-                 skip_nonfinite_grads: bool = False):
+                 skip_nonfinite_grads: bool = False,
+                 grad_accum_steps: int = 1):
         self.epochs = epochs
         self.enable_function = enable_function
         self.transformer = transformer
         self.src_tokenizer = src_tokenizer
         self.tgt_tokenizer = tgt_tokenizer
         self.batch_size = batch_size  # GLOBAL batch (loss scale, Q4)
+        # micro-batches per optimizer step; the loss of every micro-batch is
+        # still divided by the GLOBAL batch, so the micro-gradients simply
+        # sum to the full-batch gradient
+        self.grad_accum_steps = int(grad_accum_steps)
         self.label_smoothing = label_smoothing
         self.log_interval = log_interval
         self.eval_steps = eval_steps
@@ -49,7 +54,8 @@ class Train:
         self.optimizer = NoamAdam(transformer, d_model, warmup_steps,
                                   use_flat=use_flat,
                                   max_grad_norm=clip_grad_norm,
-                                  skip_nonfinite=skip_nonfinite_grads)
+                                  skip_nonfinite=skip_nonfinite_grads,
+                                  accum_steps=self.grad_accum_steps)
         self.train_loss = Mean("train_loss")
         self.test_loss = Mean("test_loss")
         self.train_accuracy = Mean("train_accuracy")
@@ -79,6 +85,59 @@ class Train:
                 and not (dist.is_available() and dist.is_initialized()
                          and dist.get_world_size() > 1))
 
+    def _grad_sync_accum(self):
+        """Hook point for the DP subclass (accumulator all-reduce)."""
+
+    def _accum_train_step(self, src, tar):
+        """One optimizer step over grad_accum_steps micro-batches:
+        consecutive ceil(B/N)-row chunks of the batch (a short tail chunk is
+        fine, empty ones are skipped), forward + backward on each with the
+        unchanged loss_function, fp32 accumulation, one optimizer step.  The
+        step loss is the sum of the micro losses and the accuracy counts are
+        summed; both come to the host once per optimizer step."""
+        n = self.grad_accum_steps
+        rows = -(-src.shape[0] // n)
+        if self._graph_eligible():
+            cap = getattr(self, "_captured", None)
+            if cap is None or not cap.fits(src, tar):
+                from .graph import CapturedAccumTrainStep
+                cap = CapturedAccumTrainStep(
+                    self.transformer, self.optimizer, self.loss_function,
+                    (rows, src.shape[1]), (rows, tar.shape[1]), self.device)
+                self._captured = cap
+            loss, c, t = cap(src, tar)
+            self.train_loss.update(loss)
+            self.train_accuracy.update(c / max(t, 1), weight=t)
+            return torch.tensor(loss)
+        sums = None
+        for i in range(n):
+            s, t = src[i * rows:(i + 1) * rows], tar[i * rows:(i + 1) * rows]
+            if s.shape[0] == 0:
+                continue
+            tar_inp, tar_real = t[:, :-1].contiguous(), t[:, 1:].contiguous()
+            predictions, _ = self.transformer((s, tar_inp), training=True)
+            loss = self.loss_function(tar_real, predictions)
+            # per micro-batch: the embedding scatter and the column-sum
+            # reductions accumulate into flat_g and need it clear
+            self.optimizer.zero_grad()
+            loss.backward()
+            self.optimizer.accumulate()
+            with torch.no_grad():
+                part = torch.cat([
+                    loss.detach().reshape(1).to(torch.float64),
+                    ops.masked_accuracy_counts_t(predictions.detach(),
+                                                 tar_real)])
+                sums = part if sums is None else sums + part
+        if sums is None:
+            raise ValueError("train_step got an empty batch")
+        self._grad_sync_accum()
+        # clip/skip (if enabled) acts on the all-reduced accumulator
+        self.optimizer.step()
+        loss, c, t = sums.tolist()      # the step's only host read
+        self.train_loss.update(loss)
+        self.train_accuracy.update(c / max(t, 1), weight=t)
+        return sums[0].to(torch.float32)
+
     def _captured_step(self, src, tar):
         cap = getattr(self, "_captured", None)
         if cap is None or not cap.fits(src, tar):
@@ -97,6 +156,8 @@ class Train:
         src, tar = inputs
         src = src.to(self.device, non_blocking=True)
         tar = tar.to(self.device, non_blocking=True)
+        if self.grad_accum_steps > 1:
+            return self._accum_train_step(src, tar)
         if self._graph_eligible():
             return self._captured_step(src, tar)
         tar_inp, tar_real = tar[:, :-1].contiguous(), tar[:, 1:].contiguous()
@@ -319,7 +380,15 @@ class DistributedTrain(Train):
         self.ddp = ddp
         if ddp is not None:
             ddp.broadcast_parameters()
+            if self.grad_accum_steps > 1:
+                # one all-reduce per bucket per OPTIMIZER step, on the
+                # accumulator, not one per micro backward
+                ddp.set_accumulate(True)
 
     def _grad_sync(self):
         if self.ddp is not None:
             self.ddp.finalize()
+
+    def _grad_sync_accum(self):
+        if self.ddp is not None:
+            self.ddp.finalize_accum(self.optimizer.acc)
