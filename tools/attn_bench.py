@@ -2,6 +2,12 @@
 
 Forward: trv=1 (tr16 reads of natural V) vs trv=0 (transposed V image).
 Backward: timed as-is.  python tools/attn_bench.py [iters]
+
+--segments [L]: sequence packing.  Lays a corpus-like sentence-length mix
+out as segment ids in rows of width L (default 256) and times forward and
+backward of the segment kernels, which skip the tiles outside each block's
+id range, against the same tokens as dense rows of width L (every tile
+computed).  python tools/attn_bench.py --segments [L] [iters]
 """
 import sys
 import time
@@ -34,7 +40,55 @@ SHAPES = [
 ]
 
 
+def segments(L, iters, B=64, H=8, dh=64):
+    """Corpus-like mix: lengths ~ 4 + geometric, mean about 17 tokens, capped
+    at L, first-fit in arrival order until a row is full."""
+    import random
+    rng = random.Random(0)
+    E = ext()
+    seg = torch.zeros(B, L, dtype=torch.int32)
+    nseg = 0
+    for b in range(B):
+        o, k = 0, 1
+        while True:
+            n = min(L, 4 + int(rng.expovariate(1 / 13.0)))
+            if o + n > L:
+                break
+            seg[b, o:o + n] = k
+            o, k = o + n, k + 1
+        nseg += k - 1
+    seg = seg.cuda()
+    fill = float((seg != 0).float().mean())
+    lens2 = sum(int((seg[b] == k).sum()) ** 2 for b in range(B)
+                for k in range(1, int(seg[b].max()) + 1))
+    print(f"L={L} B={B} H={H} dh={dh}: {nseg} segments, fill {fill:.3f}, "
+          f"sum len^2 / B*L^2 = {lens2 / (B * L * L):.3f}")
+    torch.manual_seed(0)
+    nop = torch.Tensor()
+    sc = dh ** -0.5
+    q, k, v = (torch.randn(B, L, H, dh, device="cuda", dtype=torch.bfloat16)
+               for _ in range(3))
+    for causal in (False, True):
+        o, lse = E.attn_fwd_seg(q, k, v, seg, seg, causal, sc)
+        do = torch.randn_like(o)
+        tf = timeit(lambda: E.attn_fwd_seg(q, k, v, seg, seg, causal, sc),
+                    iters)
+        tb = timeit(lambda: E.attn_bwd_seg(q, k, v, o, do, lse, seg, seg,
+                                           causal, sc, 0), iters)
+        o2, lse2 = E.attn_fwd(q, k, v, nop, causal, sc, 1)
+        df = timeit(lambda: E.attn_fwd(q, k, v, nop, causal, sc, 1), iters)
+        db = timeit(lambda: E.attn_bwd(q, k, v, o2, do, lse2, nop, causal,
+                                       sc, 0), iters)
+        print(f"causal={int(causal)}  fwd seg {tf*1e3:7.3f} ms vs dense "
+              f"{df*1e3:7.3f} ({df/tf:4.2f}x) | bwd seg {tb*1e3:7.3f} vs "
+              f"dense {db*1e3:7.3f} ({db/tb:4.2f}x)")
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--segments":
+        rest = [int(a) for a in sys.argv[2:]]
+        segments(rest[0] if rest else 256, rest[1] if len(rest) > 1 else 30)
+        return
     iters = int(sys.argv[1]) if len(sys.argv) > 1 else 30
     E = ext()
     torch.manual_seed(0)

@@ -59,7 +59,8 @@ def main(epochs, enable_function, buffer_size, batch_size, sequence_length,
          seed=1234, log_interval=100, eval_steps=50, synthetic_data=False,
          synthetic_vocab=32768, steps_per_epoch=100, max_decode_len=10,
          trace_dir=None, debug_sync=False, clip_grad_norm=0.0,
-         skip_nonfinite_grads=False, grad_accum_steps=1, **_ignored):
+         skip_nonfinite_grads=False, grad_accum_steps=1,
+         pack_sequences=False, **_ignored):
     if debug_sync:
         # race/fault localization: every kernel launch is
         # serialized and synchronous so a fault is attributed to the
@@ -73,6 +74,9 @@ def main(epochs, enable_function, buffer_size, batch_size, sequence_length,
     train_log_dir = os.path.join("logs", "gradient_tape", ts, "train")
     test_log_dir = os.path.join("logs", "gradient_tape", ts, "test")
 
+    if pack_sequences and synthetic_data:
+        raise ValueError("--pack_sequences needs a real corpus: synthetic "
+                         "rows are full-length, there is nothing to pack")
     if synthetic_data:
         src_tok = tgt_tok = _SyntheticTok(synthetic_vocab)
         train_ds = SyntheticSeq2SeqDataset(synthetic_vocab, batch_size,
@@ -84,7 +88,8 @@ def main(epochs, enable_function, buffer_size, batch_size, sequence_length,
     else:
         train_ds, test_ds, src_tok, tgt_tok = load_dataset(
             dataset_path, src_vocab_file, tgt_vocab_file,
-            sequence_length, batch_size, buffer_size, seed)
+            sequence_length, batch_size, buffer_size, seed,
+            pack_sequences=pack_sequences)
 
     input_vocab_size = src_tok.vocab_size + 2
     target_vocab_size = tgt_tok.vocab_size + 2
@@ -103,7 +108,8 @@ def main(epochs, enable_function, buffer_size, batch_size, sequence_length,
                   max_decode_len=max_decode_len,
                   clip_grad_norm=clip_grad_norm,
                   skip_nonfinite_grads=skip_nonfinite_grads,
-                  grad_accum_steps=grad_accum_steps)
+                  grad_accum_steps=grad_accum_steps,
+                  pack_sequences=pack_sequences)
     train.load_ckpt()
     train.install_signal_handler()  # SIGTERM/SIGINT -> checkpoint + exit
     if trace_dir:

@@ -103,6 +103,11 @@ def transformer_flags(parser: argparse.ArgumentParser | None = None) -> argparse
                              "split along dim 0 and the gradients are summed "
                              "in fp32; --batch_size stays the global batch "
                              "per optimizer step; 1 = off")
+    _add_bool_flag(parser, "pack_sequences", False,
+                   "pack several sentence pairs into each training row of "
+                   "width --sequence_length (segment-masked attention, "
+                   "positions restart per sentence); every optimizer step "
+                   "still consumes the same --batch_size pairs")
     return parser
 
 
@@ -142,6 +147,7 @@ def flags_dict(args: argparse.Namespace) -> dict:
         "clip_grad_norm": args.clip_grad_norm,
         "skip_nonfinite_grads": args.skip_nonfinite_grads,
         "grad_accum_steps": args.grad_accum_steps,
+        "pack_sequences": args.pack_sequences,
     }
 
 
@@ -152,4 +158,7 @@ def parse_flags(argv=None, extra=None):
     args, unknown = parser.parse_known_args(argv if argv is not None else sys.argv[1:])
     if unknown:
         print(f"[transformer_amd] ignoring unknown flags: {unknown}", file=sys.stderr)
+    if args.pack_sequences and args.synthetic_data:
+        parser.error("--pack_sequences needs a real corpus: --synthetic_data "
+                     "rows are full-length, there is nothing to pack")
     return args

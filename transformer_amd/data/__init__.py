@@ -5,4 +5,6 @@ from .dataset import (  # noqa: F401
     load_or_create_tokenizer,
     SyntheticSeq2SeqDataset,
     BatchedDataset,
+    PackedBatch,
+    pack_pairs,
 )

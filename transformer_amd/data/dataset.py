@@ -23,6 +23,7 @@ import glob
 import hashlib
 import os
 import random
+from typing import NamedTuple
 
 import torch
 
@@ -60,15 +61,100 @@ def load_or_create_tokenizer(pairs, src_vocab_file: str, tgt_vocab_file: str,
     return toks[0], toks[1]
 
 
+class PackedBatch(NamedTuple):
+    """Several sentence pairs per row, all rows of one width L.
+
+    src / tar_inp / tar_real are int64 tokens (pad id 0); *_seg are int32
+    segment ids — the pairs of a row carry 1, 2, 3, ... in order, each
+    contiguous, 0 = padding, zeros only at the tail; *_pos are int32
+    positions restarting at 0 in every sentence.  The teacher-forcing shift
+    is done per sentence BEFORE packing (t[:-1] -> tar_inp, t[1:] ->
+    tar_real), so tar_inp, tar_real, tgt_seg and tgt_pos share one layout and
+    a label never comes from the next sentence.  Pair n of a row is segment n
+    on the source and on the target side."""
+    src: torch.Tensor
+    src_seg: torch.Tensor
+    src_pos: torch.Tensor
+    tar_inp: torch.Tensor
+    tar_real: torch.Tensor
+    tgt_seg: torch.Tensor
+    tgt_pos: torch.Tensor
+
+    def to(self, device, non_blocking: bool = False):
+        return PackedBatch(*(t.to(device, non_blocking=non_blocking)
+                             for t in self))
+
+    def rows(self, lo: int, hi: int):
+        """Rows [lo, hi) of every field (gradient-accumulation chunks)."""
+        return PackedBatch(*(t[lo:hi] for t in self))
+
+    def real_tokens(self) -> int:
+        return int((self.src_seg != 0).sum() + (self.tgt_seg != 0).sum())
+
+
+def pack_pairs(pairs, width: int) -> PackedBatch:
+    """First-fit-decreasing packing of encoded (src, tgt) pairs into as few
+    rows of `width` as that needs.  Pairs are placed longest first — by
+    max(len(src), len(tgt)), ties by their order in `pairs` — each into the
+    first row where BOTH its source and its target-minus-one (the shifted
+    length) still fit.  Deterministic."""
+    for s, t in pairs:
+        if len(s) > width or len(t) - 1 > width or len(t) < 2 or not s:
+            raise ValueError(
+                f"pair of lengths ({len(s)}, {len(t)}) does not fit pack "
+                f"width {width}")
+    order = sorted(range(len(pairs)),
+                   key=lambda j: (-max(len(pairs[j][0]), len(pairs[j][1])), j))
+    rows, free = [], []   # per row: member indices, [src free, tgt free]
+    for j in order:
+        ls, lt = len(pairs[j][0]), len(pairs[j][1]) - 1
+        for r, (fs, ft) in enumerate(free):
+            if ls <= fs and lt <= ft:
+                break
+        else:
+            r = len(rows)
+            rows.append([])
+            free.append([width, width])
+        rows[r].append(j)
+        free[r][0] -= ls
+        free[r][1] -= lt
+    n = len(rows)
+    z64 = lambda: torch.zeros(n, width, dtype=torch.int64)
+    z32 = lambda: torch.zeros(n, width, dtype=torch.int32)
+    out = PackedBatch(z64(), z32(), z32(), z64(), z64(), z32(), z32())
+    for r, members in enumerate(rows):
+        so = to = 0
+        for k, j in enumerate(members, start=1):
+            s = torch.as_tensor(pairs[j][0], dtype=torch.int64)
+            t = torch.as_tensor(pairs[j][1], dtype=torch.int64)
+            ls, lt = len(s), len(t) - 1
+            out.src[r, so:so + ls] = s
+            out.src_seg[r, so:so + ls] = k
+            out.src_pos[r, so:so + ls] = torch.arange(ls, dtype=torch.int32)
+            out.tar_inp[r, to:to + lt] = t[:-1]
+            out.tar_real[r, to:to + lt] = t[1:]
+            out.tgt_seg[r, to:to + lt] = k
+            out.tgt_pos[r, to:to + lt] = torch.arange(lt, dtype=torch.int32)
+            so += ls
+            to += lt
+    return out
+
+
 class BatchedDataset:
     """Shuffle + padded-batch over encoded pairs (reference utils.py:154-159:
     shuffle(buffer).padded_batch(batch, pad id 0)).  Supports DP sharding:
     rank r of world W sees batches of batch_size//W drawn from its shard
-    (the reference's MirroredStrategy input split)."""
+    (the reference's MirroredStrategy input split).
+
+    pack_width=L: the same index lists are drawn (same shuffle, same shard,
+    same ragged-tail rules), but each step's pairs are packed into a
+    PackedBatch of width exactly L (pack_pairs) instead of being padded to
+    the longest sentence — same pairs per step, fewer and fuller rows."""
 
     def __init__(self, encoded_pairs, batch_size: int, shuffle: bool = True,
                  buffer_size: int = 100000, seed: int = 0,
-                 rank: int = 0, world_size: int = 1, drop_last: bool = False):
+                 rank: int = 0, world_size: int = 1, drop_last: bool = False,
+                 pack_width: int | None = None):
         if world_size > 1 and batch_size % world_size != 0:
             raise ValueError(  # reference distributed_train.py:154-158
                 f"Batch size {batch_size} not divisible by world size {world_size}")
@@ -80,6 +166,7 @@ class BatchedDataset:
         self.seed = seed
         self.rank, self.world_size = rank, world_size
         self.drop_last = drop_last
+        self.pack_width = pack_width
         self.epoch = 0
 
     def set_epoch(self, epoch: int):
@@ -111,6 +198,10 @@ class BatchedDataset:
             # per-replica shard of the global batch
             shard = idx[self.rank * len(idx) // self.world_size:
                         (self.rank + 1) * len(idx) // self.world_size]
+            if self.pack_width is not None:
+                yield pack_pairs([self.pairs[j] for j in shard],
+                                 self.pack_width)
+                continue
             src = [self.pairs[j][0] for j in shard]
             tgt = [self.pairs[j][1] for j in shard]
             yield _pad_batch(src), _pad_batch(tgt)
@@ -151,9 +242,11 @@ def _encode_corpus(pairs, src_tok, tgt_tok, cache_path=None):
 def load_dataset(dataset_path: str, src_vocab_file: str, tgt_vocab_file: str,
                  sequence_length: int = 50, batch_size: int = 64,
                  buffer_size: int = 100000, seed: int = 0,
-                 rank: int = 0, world_size: int = 1):
+                 rank: int = 0, world_size: int = 1,
+                 pack_sequences: bool = False):
     """Returns (train_ds, test_ds, src_tok, tgt_tok) — the reference's
-    load_dataset contract (utils.py:114-161)."""
+    load_dataset contract (utils.py:114-161).  pack_sequences packs the
+    TRAIN batches to width sequence_length; evaluation stays padded."""
     train_pairs = read_data(os.path.join(dataset_path, "src-train.txt"),
                             os.path.join(dataset_path, "tgt-train.txt"))
     test_pairs = read_data(os.path.join(dataset_path, "src-test.txt"),
@@ -188,7 +281,9 @@ def load_dataset(dataset_path: str, src_vocab_file: str, tgt_vocab_file: str,
 
     train_ds = BatchedDataset(enc_train, batch_size, shuffle=True,
                               buffer_size=buffer_size, seed=seed,
-                              rank=rank, world_size=world_size)
+                              rank=rank, world_size=world_size,
+                              pack_width=(sequence_length if pack_sequences
+                                          else None))
     test_ds = BatchedDataset(enc_test, batch_size, shuffle=False,
                              rank=rank, world_size=world_size)
     return train_ds, test_ds, src_tok, tgt_tok

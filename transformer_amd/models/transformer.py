@@ -52,17 +52,23 @@ class SelfAttention(nn.Module):
         self.b_o = nn.Parameter(torch.zeros(d_model))
 
     def forward(self, x, kv_pad=None, causal=False, return_weights=False,
-                project=True):
+                project=True, seg=None):
         """project=False returns the merged heads BEFORE the output
         projection — the layer then runs w_o/b_o fused with its
-        dropout + residual LayerNorm (one autograd node)."""
+        dropout + residual LayerNorm (one autograd node).  seg: (B,S)
+        segment ids of a packed row (replaces kv_pad)."""
         B, S, d = x.shape
         qkv = ops.linear(x, self.w_qkv, self.b_qkv)          # (B,S,3d)
         qkv = qkv.view(B, S, 3, self.num_heads, self.depth)
         # packed path: the attention kernels read q/k/v slots through strides
         # and backward emits one packed dQKV (no copies, SURVEY.md K6)
-        out = ops.self_attention(qkv, kv_pad=kv_pad, causal=causal,
-                                 return_weights=return_weights)
+        if seg is not None:
+            out = ops.self_attention(qkv, causal=causal,
+                                     return_weights=return_weights,
+                                     q_seg=seg, kv_seg=seg)
+        else:
+            out = ops.self_attention(qkv, kv_pad=kv_pad, causal=causal,
+                                     return_weights=return_weights)
         if return_weights:
             out, w = out
         out = out.reshape(B, S, d)
@@ -88,14 +94,18 @@ class CrossAttention(nn.Module):
         self.b_o = nn.Parameter(torch.zeros(d_model))
 
     def forward(self, x, enc_output, kv_pad=None, return_weights=False,
-                project=True):
+                project=True, q_seg=None, kv_seg=None):
         B, Sq, d = x.shape
         Sk = enc_output.shape[1]
         q = ops.linear(x, self.w_q, self.b_q).view(B, Sq, self.num_heads, self.depth)
         kv = ops.linear(enc_output, self.w_kv, self.b_kv)
         kv = kv.view(B, Sk, 2, self.num_heads, self.depth)
-        out = ops.cross_attention(q, kv, kv_pad=kv_pad,
-                                  return_weights=return_weights)
+        if q_seg is not None:
+            out = ops.cross_attention(q, kv, return_weights=return_weights,
+                                      q_seg=q_seg, kv_seg=kv_seg)
+        else:
+            out = ops.cross_attention(q, kv, kv_pad=kv_pad,
+                                      return_weights=return_weights)
         if return_weights:
             out, w = out
         out = out.reshape(B, Sq, d)
@@ -154,8 +164,9 @@ class EncoderLayer(nn.Module):
         self.ln2 = _LN(d_model)
         self.rate = rate
 
-    def forward(self, x, kv_pad, training):
-        heads, _ = self.mha(x, kv_pad=kv_pad, causal=False, project=False)
+    def forward(self, x, kv_pad, training, seg=None):
+        heads, _ = self.mha(x, kv_pad=kv_pad, causal=False, project=False,
+                            seg=seg)
         out1 = _proj_ln(self.mha, heads, x, self.ln1, self.rate, training)
         return _ffn_ln(self.ffn, out1, self.ln2, self.rate, training)
 
@@ -175,16 +186,24 @@ class DecoderLayer(nn.Module):
         self.rate = rate
 
     def forward(self, x, enc_output, tgt_pad, src_pad, training,
-                return_weights=False):
+                return_weights=False, tgt_seg=None, src_seg=None):
         heads1, w1 = self.mha1(x, kv_pad=tgt_pad, causal=True,
-                               return_weights=return_weights, project=False)
+                               return_weights=return_weights, project=False,
+                               seg=tgt_seg)
         out1 = _proj_ln(self.mha1, heads1, x, self.ln1, self.rate, training)
         heads2, w2 = self.mha2(out1, enc_output, kv_pad=src_pad,
-                               return_weights=return_weights, project=False)
+                               return_weights=return_weights, project=False,
+                               q_seg=tgt_seg, kv_seg=src_seg)
         out2 = _proj_ln(self.mha2, heads2, out1, self.ln2, self.rate,
                         training)
         out3 = _ffn_ln(self.ffn, out2, self.ln3, self.rate, training)
         return out3, w1, w2
+
+
+def _embed(tokens, weight, pe, positions):
+    if positions is None:
+        return ops.embedding_scale_pe(tokens, weight, pe)
+    return ops.embedding_scale_pe(tokens, weight, pe, positions=positions)
 
 
 class Encoder(nn.Module):
@@ -205,11 +224,11 @@ class Encoder(nn.Module):
             EncoderLayer(d_model, num_heads, dff, rate) for _ in range(num_layers))
         self.rate = rate
 
-    def forward(self, tokens, src_pad, training):
-        x = ops.embedding_scale_pe(tokens, self.embedding, self.pe)
+    def forward(self, tokens, src_pad, training, seg=None, positions=None):
+        x = _embed(tokens, self.embedding, self.pe, positions)
         x = ops.dropout(x, self.rate, training)
         for layer in self.layers:
-            x = layer(x, src_pad, training)
+            x = layer(x, src_pad, training, seg=seg)
         return x
 
 
@@ -231,13 +250,15 @@ class Decoder(nn.Module):
         self.rate = rate
 
     def forward(self, tokens, enc_output, tgt_pad, src_pad, training,
-                return_weights=False):
-        x = ops.embedding_scale_pe(tokens, self.embedding, self.pe)
+                return_weights=False, tgt_seg=None, src_seg=None,
+                positions=None):
+        x = _embed(tokens, self.embedding, self.pe, positions)
         x = ops.dropout(x, self.rate, training)
         attention_weights = {}
         for i, layer in enumerate(self.layers):
             x, w1, w2 = layer(x, enc_output, tgt_pad, src_pad, training,
-                              return_weights=return_weights)
+                              return_weights=return_weights,
+                              tgt_seg=tgt_seg, src_seg=src_seg)
             if return_weights:
                 attention_weights[f"decoder_layer{i + 1}_block1"] = w1
                 attention_weights[f"decoder_layer{i + 1}_block2"] = w2
@@ -248,7 +269,14 @@ class Transformer(nn.Module):
     """Top-level model (C10, reference Transformer.py:5-32).
 
     call((inp, tar), training) -> (logits, attention_weights) — the reference
-    signature; attention_weights is {} unless return_weights=True (Q13)."""
+    signature; attention_weights is {} unless return_weights=True (Q13).
+
+    A packed input (data.PackedBatch, or anything with its src / src_seg /
+    src_pos / tar_inp / tgt_seg / tgt_pos fields) holds several sentence
+    pairs per row: attention is confined to each pair by the segment ids and
+    the positional encoding restarts at every sentence, so each pair computes
+    what it would compute in a row of its own.  Logits are (B, L, V) in the
+    packed layout; tar_real of the same batch labels them."""
 
     def __init__(self, num_layers, d_model, num_heads, dff, input_vocab_size,
                  target_vocab_size, rate=0.1, max_position=4096):
@@ -260,7 +288,22 @@ class Transformer(nn.Module):
         self.w_final = nn.Parameter(_glorot(target_vocab_size, d_model))
         self.b_final = nn.Parameter(torch.zeros(target_vocab_size))
 
+    def _forward_packed(self, pb, training, return_weights):
+        i32 = torch.int32   # converted ONCE; the per-layer wrappers no-op
+        src_seg = pb.src_seg.to(i32).contiguous()
+        tgt_seg = pb.tgt_seg.to(i32).contiguous()
+        enc_output = self.encoder(pb.src, None, training, seg=src_seg,
+                                  positions=pb.src_pos.to(i32).contiguous())
+        dec_output, attention_weights = self.decoder(
+            pb.tar_inp, enc_output, None, None, training, return_weights,
+            tgt_seg=tgt_seg, src_seg=src_seg,
+            positions=pb.tgt_pos.to(i32).contiguous())
+        logits = ops.linear(dec_output, self.w_final, self.b_final)
+        return logits, attention_weights
+
     def forward(self, inputs, training=False, return_weights=False):
+        if hasattr(inputs, "src_seg"):
+            return self._forward_packed(inputs, training, return_weights)
         inp, tar = inputs
         # mask construction (C5) folds into the attention kernels' predicate
         # logic: only per-token pad flags cross the boundary.

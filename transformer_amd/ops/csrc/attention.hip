@@ -142,6 +142,80 @@ DEV_INLINE void stage_kv(const short* __restrict__ g, long row_stride,
   }
 }
 
+// ---- segment masking (sequence packing) ------------------------------------
+// A row may hold several sentences: q_seg (B,Sq) / kv_seg (B,Sk) int32 ids,
+// 1,2,3,... contiguous in order, 0 = padding, zeros only at the tail of a
+// row.  Query i sees key j iff q_seg[i] == kv_seg[j] != 0 (and j <= i under
+// causal).  Hidden keys get p = 0 by SELECTION (no additive -1e9), so an
+// id-0 query row has O = 0, dQ = 0 and feeds nothing into dK/dV.
+//
+// The three kernels are templated on SEG.  SEG=false carries an empty
+// argument struct and every segment statement sits under `if constexpr`, so
+// the unsegmented instantiations keep the code they had.  SEG=true is a
+// second instantiation of the same body: ids are monotone, so a 64-row
+// block only needs the contiguous range of the other side owned by its
+// first..last non-zero id.  attn_seg_ranges_kernel computes that range once
+// per block; the kernels read it with two scalar loads and loop over it
+// alone — tiles outside it are never staged.
+template <bool SEG> struct SegArgs {};
+template <> struct SegArgs<true> {
+  const int* q_seg;    // (B,Sq)
+  const int* kv_seg;   // (B,Sk)
+  const int* q_rng;    // (B, cdiv(Sq,64), 2): key [lo,hi) of each q-block
+  const int* kv_rng;   // (B, cdiv(Sk,64), 2): query [lo,hi) of each k-block
+};
+
+#define SEG_BLK (WAVES * QW)   // rows per range entry = block height
+
+// first index whose id is >= `id` (upper: > `id`); ids ascend, 0 sorts last
+DEV_INLINE int seg_bound(const int* ids, int n, int id, bool upper) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    int v = ids[mid];
+    if (v == 0) v = 0x7fffffff;
+    if (upper ? (v <= id) : (v < id)) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// [lo,hi) of `other` owned by the ids of own[r0 .. r0+SEG_BLK)
+DEV_INLINE void seg_block_range(const int* own, int n_own, int r0,
+                                const int* other, int n_other, int* out) {
+  const int r1 = min(r0 + SEG_BLK, n_own);
+  const int lo_id = own[r0];
+  int hi_id = 0;
+  for (int r = r1 - 1; r >= r0 && hi_id == 0; --r) hi_id = own[r];
+  if (lo_id == 0) {   // zeros only at the tail: the whole block is padding
+    out[0] = out[1] = 0;
+    return;
+  }
+  out[0] = seg_bound(other, n_other, lo_id, false);
+  out[1] = seg_bound(other, n_other, hi_id, true);
+}
+
+__global__ __launch_bounds__(256)
+void attn_seg_ranges_kernel(const int* __restrict__ q_seg,
+                            const int* __restrict__ kv_seg, int B, int Sq,
+                            int Sk, int* __restrict__ q_rng,
+                            int* __restrict__ kv_rng) {
+  const int nqb = cdiv(Sq, SEG_BLK), nkb = cdiv(Sk, SEG_BLK);
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= B * (nqb + nkb)) return;
+  const int b = idx / (nqb + nkb);
+  int j = idx % (nqb + nkb);
+  const int* qs = q_seg + (long)b * Sq;
+  const int* ks = kv_seg + (long)b * Sk;
+  if (j < nqb) {
+    seg_block_range(qs, Sq, j * SEG_BLK, ks, Sk,
+                    q_rng + ((long)b * nqb + j) * 2);
+  } else {
+    j -= nqb;
+    seg_block_range(ks, Sk, j * SEG_BLK, qs, Sq,
+                    kv_rng + ((long)b * nkb + j) * 2);
+  }
+}
+
 // ---- forward ---------------------------------------------------------------
 // TRV: read the PV B-operand from the NATURAL V image via
 // ds_read_b64_tr_b16 (no transposed staging); else build a transposed V
@@ -153,14 +227,15 @@ DEV_INLINE void stage_kv(const short* __restrict__ g, long row_stride,
 // once per q-block (16.4 GB per call at 64-row blocks), and doubling the
 // block height halves that traffic.  Softmax temporaries live per
 // row-fragment iteration; only qf/acc/m/l are duplicated.
-template <int DH, bool TRV, int RF>
+template <int DH, bool TRV, int RF, bool SEG = false>
 __global__ __launch_bounds__(256)
 void attn_fwd_kernel(const short* __restrict__ Q, const short* __restrict__ K,
                      const short* __restrict__ V,
                      const unsigned char* __restrict__ kv_pad,
                      short* __restrict__ O, float* __restrict__ LSE, int B,
                      int H, int Sq, int Sk, int causal, float scale,
-                     long q_rs, long kv_rs, long o_rs, long q_bs, long kv_bs) {
+                     long q_rs, long kv_rs, long o_rs, long q_bs, long kv_bs,
+                     SegArgs<SEG> sg) {
   constexpr int D32 = DH / 32;   // QK^T MFMA k-steps
   constexpr int D16 = DH / 16;   // O fragments
   constexpr int FKVT = 64;       // key tile
@@ -210,10 +285,45 @@ void attn_fwd_kernel(const short* __restrict__ Q, const short* __restrict__ K,
     }
 
   // causal: keys beyond this block's last row are fully masked
-  const int kend = causal ? min(Sk, (qb + 1) * (WAVES * FQW)) : Sk;
+  int kend = causal ? min(Sk, (qb + 1) * (WAVES * FQW)) : Sk;
+  int kbeg = 0;
 
-  for (int k0 = 0; k0 < kend; k0 += FKVT) {
+  // segment path: ids of this lane's 4 C-rows per fragment, the id that
+  // owns all 16 rows of a fragment (-1 if none), and the block's key range
+  int qid[RF][4], wq[RF];
+  const int* ks = nullptr;
+  if constexpr (SEG) {
+    static_assert(WAVES * FQW == SEG_BLK, "range table is per 64-row block");
+    const int* qs = sg.q_seg + (long)b * Sq;
+    ks = sg.kv_seg + (long)b * Sk;
+    const int q0u = __builtin_amdgcn_readfirstlane(q0);
+#pragma unroll
+    for (int rf = 0; rf < RF; ++rf) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = q0 + rf * 16 + kg * 4 + r;
+        qid[rf][r] = row < Sq ? qs[row] : 0;
+      }
+      const int ra = q0u + rf * 16, rz = ra + 15;
+      const int a = ra < Sq ? qs[ra] : 0, z = rz < Sq ? qs[rz] : 0;
+      wq[rf] = (a == z && a != 0) ? a : -1;
+    }
+    const int* rg = sg.q_rng + ((long)b * gridDim.y + qb) * 2;
+    kbeg = rg[0] / FKVT * FKVT;
+    kend = min(kend, rg[1]);
+  }
+
+  for (int k0 = kbeg; k0 < kend; k0 += FKVT) {
     const int kc = min(FKVT, Sk - k0);
+    // the one id that owns all 64 keys of this tile (scalar loads, issued
+    // ahead of the staging), else -1
+    int tile_id = -1;
+    if constexpr (SEG) {
+      if (kc == FKVT) {
+        const int a = ks[k0], z = ks[k0 + FKVT - 1];
+        if (a == z && a != 0) tile_id = a;
+      }
+    }
     stage_kv<DH, true, false, FKVT>(Kp + (long)k0 * kv_rs, kv_rs, kc,
                                     k_lds, nullptr);
     if (TRV)
@@ -260,8 +370,11 @@ void attn_fwd_kernel(const short* __restrict__ Q, const short* __restrict__ K,
       }
       __builtin_amdgcn_s_setprio(0);
       // clean: whole tile unmasked for this wave's rows (wave-uniform)
-      const bool clean =
+      bool clean =
           tile_full && (!causal || k0 + FKVT - 1 <= qr0 + kg * 4);
+      if constexpr (SEG)
+        clean = tile_id == wq[rf] && tile_id > 0 &&
+                (!causal || k0 + FKVT - 1 <= qr0 + kg * 4);
       if (clean) {
 #pragma unroll
         for (int half = 0; half < NHALF; ++half)
@@ -271,6 +384,24 @@ void attn_fwd_kernel(const short* __restrict__ Q, const short* __restrict__ K,
             p_raw[half][r] = x;
             tile_pmax[r] = fmaxf(tile_pmax[r], x);
           }
+      } else if constexpr (SEG) {
+        // selection: a hidden key's logit becomes -inf, so p = exp(-inf -
+        // m) is exactly 0 (m stays finite, >= -1e30) and it never moves
+        // the row max
+#pragma unroll
+        for (int half = 0; half < NHALF; ++half) {
+          const int kcol = k0 + half * 16 + fr;
+          const int kidc = kcol < Sk ? ks[kcol] : 0;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int qrow = qr0 + kg * 4 + r;
+            const bool vis = kidc == qid[rf][r] && kidc != 0 &&
+                             (!causal || kcol <= qrow);
+            float x = vis ? s2h[half][r] * scale : -INFINITY;
+            p_raw[half][r] = x;
+            tile_pmax[r] = fmaxf(tile_pmax[r], x);
+          }
+        }
       } else {
 #pragma unroll
         for (int half = 0; half < NHALF; ++half) {
@@ -437,7 +568,7 @@ void attn_bwd_dot_kernel(const short* __restrict__ dO,
 // dK/dV kernel: one 4-wave block per 64-key tile; loops q-tiles of QT
 // (32, or 64 at long sequence — halves the per-tile staging/sync fixed
 // costs, which dominate the S=4096 backward).
-template <int DH, int QT = KVT>
+template <int DH, int QT = KVT, bool SEG = false>
 __global__ __launch_bounds__(256)
 void attn_bwd_kv_kernel(const short* __restrict__ Q,
                         const short* __restrict__ K,
@@ -448,7 +579,8 @@ void attn_bwd_kv_kernel(const short* __restrict__ Q,
                         const unsigned char* __restrict__ kv_pad,
                         short* __restrict__ dK, short* __restrict__ dV, int B,
                         int H, int Sq, int Sk, int causal, float scale,
-                        long q_rs, long kv_rs, long do_rs, long dkv_rs) {
+                        long q_rs, long kv_rs, long do_rs, long dkv_rs,
+                        SegArgs<SEG> sg) {
   constexpr int D32 = DH / 32;
   constexpr int D16 = DH / 16;
   constexpr int QH = QT / 16;          // 16-q halves per tile
@@ -495,7 +627,26 @@ void attn_bwd_kv_kernel(const short* __restrict__ Q,
   }
 
   // causal: q-rows before this key-block are fully masked
-  const int q_start = causal ? (kb * (WAVES * QW)) / QT * QT : 0;
+  int q_start = causal ? (kb * (WAVES * QW)) / QT * QT : 0;
+  int q_end = Sq;
+
+  // segment path: ids of this lane's 4 OUTPUT keys, the id that owns all
+  // four (-1 if none), and the block's query range
+  int kid4[4], lane_kid = -1;
+  const int* qs = nullptr;
+  if constexpr (SEG) {
+    qs = sg.q_seg + (long)b * Sq;
+    const int* ks = sg.kv_seg + (long)b * Sk;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int key = k0w + kg * 4 + r;
+      kid4[r] = key < Sk ? ks[key] : 0;
+    }
+    if (kid4[0] == kid4[3] && kid4[0] != 0) lane_kid = kid4[0];
+    const int* rg = sg.kv_rng + ((long)b * gridDim.y + kb) * 2;
+    q_start = max(q_start, rg[0] / QT * QT);
+    q_end = min(Sq, rg[1]);
+  }
 
   // any pad among this wave's 16 OUTPUT keys (C rows k0w..k0w+15 — note
   // k_pad above is the lane's A-fragment row k0w+fr, a different role)
@@ -505,7 +656,7 @@ void attn_bwd_kv_kernel(const short* __restrict__ Q,
     wave_pad_any = __any(kk < Sk && pad[min(kk, Sk - 1)]);
   }
 
-  for (int j0 = q_start; j0 < Sq; j0 += QT) {
+  for (int j0 = q_start; j0 < q_end; j0 += QT) {
     const int jc = min(QT, Sq - j0);
     stage_kv<DH, true, false, QT>(Qp + (long)j0 * q_rs, q_rs, jc,
                                   q_lds, nullptr);
@@ -536,14 +687,33 @@ void attn_bwd_kv_kernel(const short* __restrict__ Q,
       // per-lane clean: this lane's 4 OUTPUT keys (k0w+kg*4+r) valid,
       // no pad in the wave's keys, its q col in range, and (under
       // causal) all its keys visible to that col
-      const bool clean2 = q_ok && !wave_pad_any &&
-                          (k0w + kg * 4 + 3 < Sk) &&
-                          (!causal || k0w + kg * 4 + 3 <= qcol);
+      bool clean2 = q_ok && !wave_pad_any &&
+                    (k0w + kg * 4 + 3 < Sk) &&
+                    (!causal || k0w + kg * 4 + 3 <= qcol);
+      int qidc = 0;
+      if constexpr (SEG) {
+        qidc = q_ok ? qs[qcol] : 0;
+        // lane_kid > 0 implies the lane's 4 keys are in range and unpadded
+        clean2 = lane_kid == qidc &&
+                 (!causal || k0w + kg * 4 + 3 <= qcol);
+      }
       if (clean2) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float p = __expf(st[r] * scale - lse_q);
           ds_reg[half][r] = p * (dpt[r] - d_q) * scale;
+          pw[r] = f2bfbits(p);
+        }
+      } else if constexpr (SEG) {
+        // selection: hidden pairs give p = 0 AND dS = 0, whatever st/dpt
+        // hold (out-of-range keys and columns carry id 0)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int key = k0w + kg * 4 + r;
+          const bool vis = kid4[r] == qidc && qidc != 0 &&
+                           (!causal || key <= qcol);
+          float p = vis ? __expf(st[r] * scale - lse_q) : 0.f;
+          ds_reg[half][r] = vis ? p * (dpt[r] - d_q) * scale : 0.f;
           pw[r] = f2bfbits(p);
         }
       } else {
@@ -616,7 +786,7 @@ void attn_bwd_kv_kernel(const short* __restrict__ Q,
 }
 
 // dQ kernel: one 4-wave block per 64-q tile; loops kv-tiles of QT.
-template <int DH, int QT = KVT>
+template <int DH, int QT = KVT, bool SEG = false>
 __global__ __launch_bounds__(256)
 void attn_bwd_q_kernel(const short* __restrict__ Q,
                        const short* __restrict__ K,
@@ -627,7 +797,7 @@ void attn_bwd_q_kernel(const short* __restrict__ Q,
                        const unsigned char* __restrict__ kv_pad,
                        short* __restrict__ dQ, int B, int H, int Sq, int Sk,
                        int causal, float scale, long q_rs, long kv_rs,
-                       long do_rs, long dq_rs) {
+                       long do_rs, long dq_rs, SegArgs<SEG> sg) {
   constexpr int D32 = DH / 32;
   constexpr int D16 = DH / 16;
   constexpr int QH = QT / 16;
@@ -680,9 +850,28 @@ void attn_bwd_q_kernel(const short* __restrict__ Q,
     dl_r[r] = ok ? dl[min(qrow, Sq - 1)] : 0.f;
   }
 
-  const int kend = causal ? min(Sk, qb * (WAVES * QW) + WAVES * QW) : Sk;
+  int kend = causal ? min(Sk, qb * (WAVES * QW) + WAVES * QW) : Sk;
+  int kbeg = 0;
 
-  for (int k0 = 0; k0 < kend; k0 += QT) {
+  // segment path: ids of this lane's 4 q-rows, the id that owns all four
+  // (-1 if none), and the block's key range
+  int qid4[4], lane_qid = -1;
+  const int* ks = nullptr;
+  if constexpr (SEG) {
+    const int* qs = sg.q_seg + (long)b * Sq;
+    ks = sg.kv_seg + (long)b * Sk;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int qrow = q0 + kg * 4 + r;
+      qid4[r] = qrow < Sq ? qs[qrow] : 0;
+    }
+    if (qid4[0] == qid4[3] && qid4[0] != 0) lane_qid = qid4[0];
+    const int* rg = sg.q_rng + ((long)b * gridDim.y + qb) * 2;
+    kbeg = rg[0] / QT * QT;
+    kend = min(kend, rg[1]);
+  }
+
+  for (int k0 = kbeg; k0 < kend; k0 += QT) {
     const int kc = min(QT, Sk - k0);
     stage_kv<DH, true, false, QT>(Kp + (long)k0 * kv_rs, kv_rs, kc,
                                   k_lds, nullptr);
@@ -707,13 +896,29 @@ void attn_bwd_q_kernel(const short* __restrict__ Q,
       const bool col_pad = (kcol >= Sk) || (pad && pad[min(kcol, Sk - 1)]);
       // per-lane clean: col valid+unpadded, all 4 q rows in range and
       // (under causal) at/after this key col
-      const bool clean2 = !col_pad && (q0 + kg * 4 + 3 < Sq) &&
-                          (!causal || kcol <= q0 + kg * 4);
+      bool clean2 = !col_pad && (q0 + kg * 4 + 3 < Sq) &&
+                    (!causal || kcol <= q0 + kg * 4);
+      int kidc = 0;
+      if constexpr (SEG) {
+        kidc = kcol < Sk ? ks[kcol] : 0;
+        // lane_qid > 0 implies the lane's 4 q-rows are in range
+        clean2 = kidc == lane_qid && (!causal || kcol <= q0 + kg * 4);
+      }
       if (clean2) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float p = __expf(s[r] * scale - lse_r[r]);
           dsw[r] = f2bfbits(p * (dp[r] - dl_r[r]) * scale);
+        }
+      } else if constexpr (SEG) {
+        // selection: hidden pairs give dS = 0 whatever s/dp hold
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int qrow = q0 + kg * 4 + r;
+          const bool vis = qid4[r] == kidc && kidc != 0 &&
+                           (!causal || kcol <= qrow);
+          float p = vis ? __expf(s[r] * scale - lse_r[r]) : 0.f;
+          dsw[r] = vis ? f2bfbits(p * (dp[r] - dl_r[r]) * scale) : (short)0;
         }
       } else {
 #pragma unroll
@@ -782,12 +987,44 @@ static void check_attn_batch(const torch::Tensor& t, const char* name) {
               name, " batch stride must equal S * row stride");
 }
 
+// Validates the (B,Sq) / (B,Sk) int32 id arrays, launches the range kernel
+// and returns the kernel argument struct; `keep` holds the range tables.
+// The ids' ORDER (ascending, zeros last) is the caller's contract: it lives
+// on the device and is not checked.  A violation gives wrong numbers but
+// every range is clamped to [0,S], so no access leaves the tensors.
+static SegArgs<true> seg_prepare(const torch::Tensor& q_seg,
+                                 const torch::Tensor& kv_seg, int B, int Sq,
+                                 int Sk, hipStream_t stream,
+                                 torch::Tensor& keep) {
+  TORCH_CHECK(q_seg.is_cuda() && kv_seg.is_cuda() &&
+              q_seg.dtype() == torch::kInt32 &&
+              kv_seg.dtype() == torch::kInt32 && q_seg.is_contiguous() &&
+              kv_seg.is_contiguous(),
+              "q_seg/kv_seg must be contiguous int32 GPU tensors");
+  TORCH_CHECK(q_seg.dim() == 2 && q_seg.size(0) == B && q_seg.size(1) == Sq,
+              "q_seg must be (B,Sq)");
+  TORCH_CHECK(kv_seg.dim() == 2 && kv_seg.size(0) == B &&
+              kv_seg.size(1) == Sk, "kv_seg must be (B,Sk)");
+  const int nqb = cdiv(Sq, SEG_BLK), nkb = cdiv(Sk, SEG_BLK);
+  keep = torch::empty({(long)B * (nqb + nkb) * 2}, q_seg.options());
+  SegArgs<true> sg;
+  sg.q_seg = q_seg.data_ptr<int>();
+  sg.kv_seg = kv_seg.data_ptr<int>();
+  int* base = keep.data_ptr<int>();
+  sg.q_rng = base;
+  sg.kv_rng = base + (long)B * nqb * 2;
+  attn_seg_ranges_kernel<<<cdiv(B * (nqb + nkb), 256), 256, 0, stream>>>(
+      sg.q_seg, sg.kv_seg, B, Sq, Sk, base, base + (long)B * nqb * 2);
+  return sg;
+}
+
 // q (B,Sq,H,dh), k/v (B,Sk,H,dh) — possibly strided views (e.g. slots of a
 // packed (B,S,3,H,dh) QKV tensor); k and v must share their row stride.
-std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k,
-                                    torch::Tensor v, torch::Tensor kv_pad,
-                                    bool causal, double scale,
-                                    int64_t trv) {
+// With q_seg/kv_seg defined the SEG instantiation runs and kv_pad is unused.
+static std::vector<torch::Tensor> attn_fwd_impl(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor kv_pad,
+    torch::Tensor q_seg, torch::Tensor kv_seg, bool causal, double scale,
+    int64_t trv) {
   const int B = q.size(0), Sq = q.size(1), H = q.size(2), DH = q.size(3);
   const int Sk = k.size(1);
   check_attn_view(q, DH, "q");
@@ -811,6 +1048,20 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k,
   const bool rf2 = false;
   dim3 grid(B * H, cdiv(Sq, WAVES * (rf2 ? 32 : 16)));
   auto stream = at::hip::getCurrentHIPStream();
+  if (q_seg.defined()) {
+    TORCH_CHECK(!causal || Sq == Sk, "causal segments require Sq == Sk");
+    torch::Tensor rng;
+    SegArgs<true> sg = seg_prepare(q_seg, kv_seg, B, Sq, Sk, stream, rng);
+    DISPATCH_DH(DH, {
+      attn_fwd_kernel<DHC, true, 1, true><<<grid, 256, 0, stream>>>(
+          (const short*)q.data_ptr(), (const short*)k.data_ptr(),
+          (const short*)v.data_ptr(), nullptr, (short*)o.data_ptr(),
+          lse.data_ptr<float>(), B, H, Sq, Sk, causal ? 1 : 0, (float)scale,
+          q.stride(1), k.stride(1), (long)H * DH, q.stride(0), k.stride(0),
+          sg);
+    });
+    return {o, lse};
+  }
   DISPATCH_DH(DH, {
     auto launch = [&](auto trv_c, auto rf_c) {
       attn_fwd_kernel<DHC, decltype(trv_c)::value, decltype(rf_c)::value>
@@ -819,7 +1070,7 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k,
               (const short*)v.data_ptr(), pad, (short*)o.data_ptr(),
               lse.data_ptr<float>(), B, H, Sq, Sk, causal ? 1 : 0,
               (float)scale, q.stride(1), k.stride(1), (long)H * DH,
-              q.stride(0), k.stride(0));
+              q.stride(0), k.stride(0), SegArgs<false>{});
     };
     using TT = std::true_type;
     using FF = std::false_type;
@@ -831,15 +1082,32 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k,
   return {o, lse};
 }
 
+std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k,
+                                    torch::Tensor v, torch::Tensor kv_pad,
+                                    bool causal, double scale,
+                                    int64_t trv) {
+  return attn_fwd_impl(q, k, v, kv_pad, torch::Tensor(), torch::Tensor(),
+                       causal, scale, trv);
+}
+
+std::vector<torch::Tensor> attn_fwd_seg(torch::Tensor q, torch::Tensor k,
+                                        torch::Tensor v, torch::Tensor q_seg,
+                                        torch::Tensor kv_seg, bool causal,
+                                        double scale) {
+  TORCH_CHECK(q_seg.defined() && kv_seg.defined());
+  return attn_fwd_impl(q, k, v, torch::Tensor(), q_seg, kv_seg, causal,
+                       scale, 1);
+}
+
 // mode 0: dq, dk, dv separate contiguous tensors.
 // mode 1: one packed dqkv (B,Sq,3,H,dh) — the self-attention path, gradient
 //         flows straight into the packed-QKV linear with no cat/stack.
 // mode 2: dq (B,Sq,H,dh) + packed dkv (B,Sk,2,H,dh) — the cross-attn path.
-std::vector<torch::Tensor> attn_bwd(torch::Tensor q, torch::Tensor k,
-                                    torch::Tensor v, torch::Tensor o,
-                                    torch::Tensor dout, torch::Tensor lse,
-                                    torch::Tensor kv_pad, bool causal,
-                                    double scale, int64_t mode) {
+static std::vector<torch::Tensor> attn_bwd_impl(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor o,
+    torch::Tensor dout, torch::Tensor lse, torch::Tensor kv_pad,
+    torch::Tensor q_seg, torch::Tensor kv_seg, bool causal, double scale,
+    int64_t mode) {
   const int B = q.size(0), Sq = q.size(1), H = q.size(2), DH = q.size(3);
   const int Sk = k.size(1);
   check_attn_view(q, DH, "q");
@@ -905,6 +1173,31 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor q, torch::Tensor k,
   }();
   const bool qt64 = qt_force ? (qt_force == 64)
                              : (Sq >= 1024 && Sk >= 1024);
+  if (q_seg.defined()) {
+    TORCH_CHECK(!causal || Sq == Sk, "causal segments require Sq == Sk");
+    torch::Tensor rng;
+    SegArgs<true> sg = seg_prepare(q_seg, kv_seg, B, Sq, Sk, stream, rng);
+    DISPATCH_DH(DH, {
+      auto run = [&](auto qtc) {
+        constexpr int QTC = decltype(qtc)::value;
+        attn_bwd_kv_kernel<DHC, QTC, true><<<grid_kv, 256, 0, stream>>>(
+            (const short*)q.data_ptr(), (const short*)k.data_ptr(),
+            (const short*)v.data_ptr(), (const short*)dout.data_ptr(),
+            lse.data_ptr<float>(), dl.data_ptr<float>(), nullptr, dk_p, dv_p,
+            B, H, Sq, Sk, causal ? 1 : 0, (float)scale, q_rs, kv_rs, do_rs,
+            dkv_rs, sg);
+        attn_bwd_q_kernel<DHC, QTC, true><<<grid_q, 256, 0, stream>>>(
+            (const short*)q.data_ptr(), (const short*)k.data_ptr(),
+            (const short*)v.data_ptr(), (const short*)dout.data_ptr(),
+            lse.data_ptr<float>(), dl.data_ptr<float>(), nullptr, dq_p, B, H,
+            Sq, Sk, causal ? 1 : 0, (float)scale, q_rs, kv_rs, do_rs, dq_rs,
+            sg);
+      };
+      if (qt64) run(std::integral_constant<int, 64>{});
+      else run(std::integral_constant<int, 32>{});
+    });
+    return outs;
+  }
   DISPATCH_DH(DH, {
     auto run = [&](auto qtc) {
       constexpr int QTC = decltype(qtc)::value;
@@ -913,15 +1206,36 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor q, torch::Tensor k,
           (const short*)v.data_ptr(), (const short*)dout.data_ptr(),
           lse.data_ptr<float>(), dl.data_ptr<float>(), pad, dk_p, dv_p, B,
           H, Sq, Sk, causal ? 1 : 0, (float)scale, q_rs, kv_rs, do_rs,
-          dkv_rs);
+          dkv_rs, SegArgs<false>{});
       attn_bwd_q_kernel<DHC, QTC><<<grid_q, 256, 0, stream>>>(
           (const short*)q.data_ptr(), (const short*)k.data_ptr(),
           (const short*)v.data_ptr(), (const short*)dout.data_ptr(),
           lse.data_ptr<float>(), dl.data_ptr<float>(), pad, dq_p, B, H, Sq,
-          Sk, causal ? 1 : 0, (float)scale, q_rs, kv_rs, do_rs, dq_rs);
+          Sk, causal ? 1 : 0, (float)scale, q_rs, kv_rs, do_rs, dq_rs,
+          SegArgs<false>{});
     };
     if (qt64) run(std::integral_constant<int, 64>{});
     else run(std::integral_constant<int, 32>{});
   });
   return outs;
+}
+
+std::vector<torch::Tensor> attn_bwd(torch::Tensor q, torch::Tensor k,
+                                    torch::Tensor v, torch::Tensor o,
+                                    torch::Tensor dout, torch::Tensor lse,
+                                    torch::Tensor kv_pad, bool causal,
+                                    double scale, int64_t mode) {
+  return attn_bwd_impl(q, k, v, o, dout, lse, kv_pad, torch::Tensor(),
+                       torch::Tensor(), causal, scale, mode);
+}
+
+std::vector<torch::Tensor> attn_bwd_seg(torch::Tensor q, torch::Tensor k,
+                                        torch::Tensor v, torch::Tensor o,
+                                        torch::Tensor dout, torch::Tensor lse,
+                                        torch::Tensor q_seg,
+                                        torch::Tensor kv_seg, bool causal,
+                                        double scale, int64_t mode) {
+  TORCH_CHECK(q_seg.defined() && kv_seg.defined());
+  return attn_bwd_impl(q, k, v, o, dout, lse, torch::Tensor(), q_seg, kv_seg,
+                       causal, scale, mode);
 }

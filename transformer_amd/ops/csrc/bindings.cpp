@@ -62,9 +62,20 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor q, torch::Tensor k,
                                     torch::Tensor dout, torch::Tensor lse,
                                     torch::Tensor kv_pad, bool causal,
                                     double scale, int64_t mode);
+std::vector<torch::Tensor> attn_fwd_seg(torch::Tensor q, torch::Tensor k,
+                                        torch::Tensor v, torch::Tensor q_seg,
+                                        torch::Tensor kv_seg, bool causal,
+                                        double scale);
+std::vector<torch::Tensor> attn_bwd_seg(torch::Tensor q, torch::Tensor k,
+                                        torch::Tensor v, torch::Tensor o,
+                                        torch::Tensor dout, torch::Tensor lse,
+                                        torch::Tensor q_seg,
+                                        torch::Tensor kv_seg, bool causal,
+                                        double scale, int64_t mode);
 
 torch::Tensor embed_pe_fwd(torch::Tensor tokens, torch::Tensor weight,
-                           torch::Tensor pe);
+                           torch::Tensor pe,
+                           c10::optional<torch::Tensor> positions);
 torch::Tensor embed_pe_bwd(torch::Tensor dy, torch::Tensor tokens,
                            int64_t vocab,
                            c10::optional<torch::Tensor> out);
@@ -204,7 +215,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("v"), pybind11::arg("o"), pybind11::arg("dout"),
         pybind11::arg("lse"), pybind11::arg("kv_pad"), pybind11::arg("causal"),
         pybind11::arg("scale"), pybind11::arg("mode") = 0);
-  m.def("embed_pe_fwd", &embed_pe_fwd);
+  m.def("attn_fwd_seg", &attn_fwd_seg,
+        "attn_fwd with int32 segment ids (B,Sq)/(B,Sk), 0 = pad: a query "
+        "sees the keys of its own non-zero id only (selection, not -1e9); "
+        "tiles outside a block's id range are skipped",
+        pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"),
+        pybind11::arg("q_seg"), pybind11::arg("kv_seg"),
+        pybind11::arg("causal"), pybind11::arg("scale"));
+  m.def("attn_bwd_seg", &attn_bwd_seg, pybind11::arg("q"),
+        pybind11::arg("k"), pybind11::arg("v"), pybind11::arg("o"),
+        pybind11::arg("dout"), pybind11::arg("lse"), pybind11::arg("q_seg"),
+        pybind11::arg("kv_seg"), pybind11::arg("causal"),
+        pybind11::arg("scale"), pybind11::arg("mode") = 0);
+  m.def("embed_pe_fwd", &embed_pe_fwd, pybind11::arg("tokens"),
+        pybind11::arg("weight"), pybind11::arg("pe"),
+        pybind11::arg("positions") = pybind11::none());
   m.def("embed_pe_bwd", &embed_pe_bwd, pybind11::arg("dy"),
         pybind11::arg("tokens"), pybind11::arg("vocab"),
         pybind11::arg("out") = pybind11::none());

@@ -10,12 +10,16 @@ __global__ __launch_bounds__(256)
 void embed_pe_fwd_kernel(const long* __restrict__ tokens,
                          const short* __restrict__ weight,
                          const short* __restrict__ pe,
+                         const int* __restrict__ positions, int P,
                          short* __restrict__ y, int S, int D, long n_rows,
                          float scale) {
   const long row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= n_rows) return;
   const int lane = threadIdx.x & 63;
-  const int s = row % S;  // position within the sequence
+  int s = row % S;  // position within the sequence
+  // packed rows: the position restarts at every sentence; clamped into the
+  // table, since the values live on the device and cannot be checked
+  if (positions) s = min(max(positions[row], 0), P - 1);
   const long tok = tokens[row];
   const short* wrow = weight + tok * D;
   const short* perow = pe + (long)s * D;
@@ -59,20 +63,29 @@ __global__ void cast_f32_bf16_kernel(const float* __restrict__ in,
 }
 
 torch::Tensor embed_pe_fwd(torch::Tensor tokens, torch::Tensor weight,
-                           torch::Tensor pe) {
+                           torch::Tensor pe,
+                           c10::optional<torch::Tensor> positions) {
   TORCH_CHECK(tokens.is_cuda() && tokens.dtype() == torch::kInt64 &&
               tokens.dim() == 2 && tokens.is_contiguous());
   TORCH_CHECK(weight.dtype() == torch::kBFloat16 && weight.is_contiguous());
   TORCH_CHECK(pe.dtype() == torch::kBFloat16 && pe.is_contiguous());
   const int B = tokens.size(0), S = tokens.size(1), D = weight.size(1);
   TORCH_CHECK(pe.size(0) >= S, "PE table shorter than sequence");
+  const int* pos = nullptr;
+  if (positions.has_value()) {
+    const auto& pt = *positions;
+    TORCH_CHECK(pt.is_cuda() && pt.dtype() == torch::kInt32 &&
+                pt.is_contiguous() && pt.dim() == 2 && pt.size(0) == B &&
+                pt.size(1) == S, "positions must be (B,S) int32 on GPU");
+    pos = pt.data_ptr<int>();
+  }
   auto y = torch::empty({B, S, D}, weight.options());
   long n_rows = (long)B * S;
   auto stream = at::hip::getCurrentHIPStream();
   embed_pe_fwd_kernel<<<cdiv(n_rows, 4), 256, 0, stream>>>(
       tokens.data_ptr<long>(), (const short*)weight.data_ptr(),
-      (const short*)pe.data_ptr(), (short*)y.data_ptr(), S, D, n_rows,
-      sqrtf((float)D));
+      (const short*)pe.data_ptr(), pos, (int)pe.size(0),
+      (short*)y.data_ptr(), S, D, n_rows, sqrtf((float)D));
   return y;
 }
 

@@ -195,26 +195,47 @@ def linear(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor | None = None,
 # eliminated.
 # ---------------------------------------------------------------------------
 
+def _attn_fwd(E, q, k, v, kv_pad, q_seg, kv_seg, causal, scale):
+    """Forward kernel: the segment instantiation when ids are given (kv_pad
+    is then unused: id 0 is the padding), else today's call unchanged."""
+    if q_seg is not None:
+        return E.attn_fwd_seg(q, k, v, q_seg, kv_seg, causal, scale)
+    return E.attn_fwd(q, k, v,
+                      kv_pad if kv_pad is not None else torch.Tensor(),
+                      causal, scale)
+
+
+def _attn_bwd(E, q, k, v, o, do, lse, kv_pad, q_seg, kv_seg, causal, scale,
+              mode):
+    if q_seg.numel():
+        return E.attn_bwd_seg(q, k, v, o, do, lse, q_seg, kv_seg, causal,
+                              scale, mode)
+    return E.attn_bwd(q, k, v, o, do, lse, kv_pad, causal, scale, mode)
+
+
+def _opt(t):
+    return t if t is not None else torch.Tensor()
+
+
 class _AttentionFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, kv_pad, causal, scale):
+    def forward(ctx, q, k, v, kv_pad, causal, scale, q_seg=None,
+                kv_seg=None):
         E = ext()
-        o, lse = E.attn_fwd(q, k, v,
-                            kv_pad if kv_pad is not None else torch.Tensor(),
-                            causal, scale)
+        o, lse = _attn_fwd(E, q, k, v, kv_pad, q_seg, kv_seg, causal, scale)
         ctx.causal = causal
         ctx.scale = scale
-        ctx.save_for_backward(q, k, v, o, lse,
-                              kv_pad if kv_pad is not None else torch.Tensor())
+        ctx.save_for_backward(q, k, v, o, lse, _opt(kv_pad), _opt(q_seg),
+                              _opt(kv_seg))
         return o
 
     @staticmethod
     def backward(ctx, do):
         E = ext()
-        q, k, v, o, lse, kv_pad = ctx.saved_tensors
-        dq, dk, dv = E.attn_bwd(q, k, v, o, do.contiguous(), lse, kv_pad,
-                                ctx.causal, ctx.scale, 0)
-        return dq, dk, dv, None, None, None
+        q, k, v, o, lse, kv_pad, q_seg, kv_seg = ctx.saved_tensors
+        dq, dk, dv = _attn_bwd(E, q, k, v, o, do.contiguous(), lse, kv_pad,
+                               q_seg, kv_seg, ctx.causal, ctx.scale, 0)
+        return dq, dk, dv, None, None, None, None, None
 
 
 class _SelfAttnPackedFn(torch.autograd.Function):
@@ -223,85 +244,121 @@ class _SelfAttnPackedFn(torch.autograd.Function):
     writes one packed dQKV (no cat/stack kernels)."""
 
     @staticmethod
-    def forward(ctx, qkv, kv_pad, causal, scale):
+    def forward(ctx, qkv, kv_pad, causal, scale, seg=None):
         E = ext()
         q, k, v = qkv.unbind(dim=2)  # strided views, never materialized
-        o, lse = E.attn_fwd(q, k, v,
-                            kv_pad if kv_pad is not None else torch.Tensor(),
-                            causal, scale)
+        o, lse = _attn_fwd(E, q, k, v, kv_pad, seg, seg, causal, scale)
         ctx.causal = causal
         ctx.scale = scale
-        ctx.save_for_backward(qkv, o, lse,
-                              kv_pad if kv_pad is not None else torch.Tensor())
+        ctx.save_for_backward(qkv, o, lse, _opt(kv_pad), _opt(seg))
         return o
 
     @staticmethod
     def backward(ctx, do):
         E = ext()
-        qkv, o, lse, kv_pad = ctx.saved_tensors
+        qkv, o, lse, kv_pad, seg = ctx.saved_tensors
         q, k, v = qkv.unbind(dim=2)
-        (dqkv,) = E.attn_bwd(q, k, v, o, do.contiguous(), lse, kv_pad,
-                             ctx.causal, ctx.scale, 1)
-        return dqkv, None, None, None
+        (dqkv,) = _attn_bwd(E, q, k, v, o, do.contiguous(), lse, kv_pad,
+                            seg, seg, ctx.causal, ctx.scale, 1)
+        return dqkv, None, None, None, None
 
 
 class _CrossAttnPackedFn(torch.autograd.Function):
     """Cross attention: q (B,Sq,H,dh) + packed kv (B,Sk,2,H,dh)."""
 
     @staticmethod
-    def forward(ctx, q, kv, kv_pad, scale):
+    def forward(ctx, q, kv, kv_pad, scale, q_seg=None, kv_seg=None):
         E = ext()
         k, v = kv.unbind(dim=2)
-        o, lse = E.attn_fwd(q, k, v,
-                            kv_pad if kv_pad is not None else torch.Tensor(),
-                            False, scale)
+        o, lse = _attn_fwd(E, q, k, v, kv_pad, q_seg, kv_seg, False, scale)
         ctx.scale = scale
-        ctx.save_for_backward(q, kv, o, lse,
-                              kv_pad if kv_pad is not None else torch.Tensor())
+        ctx.save_for_backward(q, kv, o, lse, _opt(kv_pad), _opt(q_seg),
+                              _opt(kv_seg))
         return o
 
     @staticmethod
     def backward(ctx, do):
         E = ext()
-        q, kv, o, lse, kv_pad = ctx.saved_tensors
+        q, kv, o, lse, kv_pad, q_seg, kv_seg = ctx.saved_tensors
         k, v = kv.unbind(dim=2)
-        dq, dkv = E.attn_bwd(q, k, v, o, do.contiguous(), lse, kv_pad,
-                             False, ctx.scale, 2)
-        return dq, dkv, None, None
+        dq, dkv = _attn_bwd(E, q, k, v, o, do.contiguous(), lse, kv_pad,
+                            q_seg, kv_seg, False, ctx.scale, 2)
+        return dq, dkv, None, None, None, None
 
 
-def self_attention(qkv, kv_pad=None, causal=False, return_weights=False):
-    """qkv: (B,S,3,H,dh).  GPU path never materializes q/k/v copies."""
+def _seg_ids(q_seg, kv_seg):
+    """Both or neither; int32 contiguous for the kernels."""
+    if (q_seg is None) != (kv_seg is None):
+        raise ValueError("q_seg and kv_seg must be given together")
+    if q_seg is None:
+        return None, None
+    return (q_seg.to(torch.int32).contiguous(),
+            kv_seg.to(torch.int32).contiguous())
+
+
+def self_attention(qkv, kv_pad=None, causal=False, return_weights=False,
+                   q_seg=None, kv_seg=None):
+    """qkv: (B,S,3,H,dh).  GPU path never materializes q/k/v copies.
+    q_seg/kv_seg: (B,S) segment ids of a packed row (see fused_attention);
+    self-attention passes the same array for both."""
     B, S, _, H, dh = qkv.shape
     scale = 1.0 / math.sqrt(dh)
     if qkv.is_cuda and not return_weights:
+        if q_seg is not None:
+            if kv_seg is not q_seg and not torch.equal(q_seg, kv_seg):
+                raise ValueError("self_attention needs q_seg == kv_seg")
+            seg, _ = _seg_ids(q_seg, q_seg)
+            return _SelfAttnPackedFn.apply(qkv, None, causal, scale, seg)
         kp = kv_pad.to(torch.uint8).contiguous() if kv_pad is not None else None
         return _SelfAttnPackedFn.apply(qkv, kp, causal, scale)
     q, k, v = qkv.unbind(dim=2)
     return fused_attention(q, k, v, kv_pad=kv_pad, causal=causal,
-                           return_weights=return_weights)
+                           return_weights=return_weights, q_seg=q_seg,
+                           kv_seg=kv_seg)
 
 
-def cross_attention(q, kv, kv_pad=None, return_weights=False):
-    """q: (B,Sq,H,dh); kv: (B,Sk,2,H,dh)."""
+def cross_attention(q, kv, kv_pad=None, return_weights=False, q_seg=None,
+                    kv_seg=None):
+    """q: (B,Sq,H,dh); kv: (B,Sk,2,H,dh).  q_seg (B,Sq) / kv_seg (B,Sk):
+    target / source segment ids of a packed row; pair n is id n on both."""
     dh = q.shape[-1]
     scale = 1.0 / math.sqrt(dh)
     if q.is_cuda and not return_weights:
+        if q_seg is not None or kv_seg is not None:
+            qs, ks = _seg_ids(q_seg, kv_seg)
+            return _CrossAttnPackedFn.apply(q.contiguous(), kv, None, scale,
+                                            qs, ks)
         kp = kv_pad.to(torch.uint8).contiguous() if kv_pad is not None else None
         return _CrossAttnPackedFn.apply(q.contiguous(), kv, kp, scale)
     k, v = kv.unbind(dim=2)
     return fused_attention(q, k, v, kv_pad=kv_pad, causal=False,
-                           return_weights=return_weights)
+                           return_weights=return_weights, q_seg=q_seg,
+                           kv_seg=kv_seg)
 
 
-def fused_attention(q, k, v, kv_pad=None, causal=False, return_weights=False):
+def fused_attention(q, k, v, kv_pad=None, causal=False, return_weights=False,
+                    q_seg=None, kv_seg=None):
     """q: (B,Sq,H,dh), k/v: (B,Sk,H,dh); kv_pad: (B,Sk) bool/uint8, True=pad.
 
     Masking semantics match reference Attention.py:25-26: masked logits get
     -1e9 added before softmax. Returns (B,Sq,H,dh); attention weights only on
-    the eager/inspection path."""
+    the eager/inspection path.
+
+    q_seg (B,Sq) / kv_seg (B,Sk): integer segment ids of packed rows (1,2,..
+    contiguous in order, 0 = padding, zeros only at the tail).  A query sees
+    exactly the keys of its own non-zero id (and, under `causal`, those at or
+    before it); kv_pad is then ignored.  Hidden keys get weight exactly 0,
+    and an id-0 query row yields a zero output row and zero gradients — not
+    the additive rule's uniform attention."""
     scale = 1.0 / math.sqrt(q.shape[-1])
+    if (q_seg is None) != (kv_seg is None):
+        raise ValueError("q_seg and kv_seg must be given together")
     if q.is_cuda and not return_weights:
+        if q_seg is not None:
+            qs, ks = _seg_ids(q_seg, kv_seg)
+            return _AttentionFn.apply(q.contiguous(), k.contiguous(),
+                                      v.contiguous(), None, causal, scale,
+                                      qs, ks)
         kp = kv_pad.to(torch.uint8).contiguous() if kv_pad is not None else None
         return _AttentionFn.apply(q.contiguous(), k.contiguous(), v.contiguous(),
                                   kp, causal, scale)
@@ -310,16 +367,27 @@ def fused_attention(q, k, v, kv_pad=None, causal=False, return_weights=False):
     mask = None
     B, Sq, H, _ = q.shape
     Sk = k.shape[1]
-    if kv_pad is not None:
-        mask = kv_pad.to(torch.float32)[:, None, None, :]
-    if causal:
-        la = R.create_look_ahead_mask(Sq, device=q.device)
-        assert Sq == Sk, "causal attention requires Sq == Sk"
-        mask = la[None, None] if mask is None else torch.maximum(mask, la[None, None])
+    if q_seg is not None:
+        # the equivalent dense mask; fp32 exp(-1e9 - max) is exactly 0, so
+        # visible rows match the kernels' selection, and id-0 query rows
+        # (uniform under the additive rule) are zeroed below
+        assert not causal or Sq == Sk, "causal attention requires Sq == Sk"
+        mask = R.create_segment_mask(q_seg, kv_seg, causal)
+    else:
+        if kv_pad is not None:
+            mask = kv_pad.to(torch.float32)[:, None, None, :]
+        if causal:
+            la = R.create_look_ahead_mask(Sq, device=q.device)
+            assert Sq == Sk, "causal attention requires Sq == Sk"
+            mask = la[None, None] if mask is None else torch.maximum(mask, la[None, None])
     if q.dtype in (torch.bfloat16, torch.float16):
         qt, kt, vt = qt.float(), kt.float(), vt.float()
     out, w = R.scaled_dot_product_attention(qt, kt, vt, mask,
                                             return_weights=True)
+    if q_seg is not None:
+        live = (q_seg != 0)[:, None, :, None]
+        out = out * live.to(out.dtype)
+        w = w * live.to(w.dtype)
     out = out.permute(0, 2, 1, 3).to(q.dtype)
     if return_weights:
         return out, w
@@ -550,12 +618,15 @@ class _EmbedPEFn(torch.autograd.Function):
     thread the graph."""
 
     @staticmethod
-    def forward(ctx, tokens, weight, hidden, pe):
+    def forward(ctx, tokens, weight, hidden, pe, positions=None):
         E = ext()
         ctx.flat = hidden is not None
         if ctx.flat:
             (weight,) = hidden
-        y = E.embed_pe_fwd(tokens, weight, pe)
+        if positions is not None:
+            y = E.embed_pe_fwd(tokens, weight, pe, positions)
+        else:
+            y = E.embed_pe_fwd(tokens, weight, pe)
         ctx.weight = weight
         ctx.save_for_backward(tokens)
         return y
@@ -570,7 +641,7 @@ class _EmbedPEFn(torch.autograd.Function):
         if ctx.flat:
             _grad_ready(weight)
             dw = None
-        return None, dw, None, None
+        return None, dw, None, None, None
 
 
 def embedding_scale_pe_at(tokens, weight, pe, pos: int):
@@ -580,17 +651,25 @@ def embedding_scale_pe_at(tokens, weight, pe, pos: int):
                               pe[pos:pos + tokens.shape[1]].contiguous())
 
 
-def embedding_scale_pe(tokens, weight, pe):
-    """tokens (B,S) int; weight (V,d); pe (P,d) fp32 table, P >= S."""
+def embedding_scale_pe(tokens, weight, pe, positions=None):
+    """tokens (B,S) int; weight (V,d); pe (P,d) fp32 table, P >= S.
+    positions (B,S) int, optional: the PE row of each token (packed rows,
+    where the position restarts at every sentence) instead of its column."""
     if weight.is_cuda:
+        extra = ()
+        if positions is not None:
+            extra = (positions.to(torch.int32).contiguous(),)
         if _flat(weight) is not None and torch.is_grad_enabled():
             marker = torch.empty(0, device=weight.device,
                                  dtype=weight.dtype, requires_grad=True)
-            return _EmbedPEFn.apply(tokens.contiguous(), marker, [weight], pe)
-        return _EmbedPEFn.apply(tokens.contiguous(), weight, None, pe)
+            return _EmbedPEFn.apply(tokens.contiguous(), marker, [weight], pe,
+                                    *extra)
+        return _EmbedPEFn.apply(tokens.contiguous(), weight, None, pe, *extra)
     if weight.dtype in (torch.bfloat16, torch.float16):
-        return R.embedding_scale_pe(tokens, weight.float(), pe[None].float()).to(weight.dtype)
-    return R.embedding_scale_pe(tokens, weight, pe[None].to(weight.dtype))
+        return R.embedding_scale_pe(tokens, weight.float(), pe[None].float(),
+                                    positions).to(weight.dtype)
+    return R.embedding_scale_pe(tokens, weight, pe[None].to(weight.dtype),
+                                positions)
 
 
 # ---------------------------------------------------------------------------

@@ -59,6 +59,23 @@ def create_masks(inp: torch.Tensor, tar: torch.Tensor):
     return enc_padding_mask, combined_mask, dec_padding_mask
 
 
+def create_segment_mask(q_seg: torch.Tensor, kv_seg: torch.Tensor,
+                        causal: bool = False) -> torch.Tensor:
+    """Packed rows: (B,Sq) / (B,Sk) integer segment ids, 0 = padding ->
+    (B, 1, Sq, Sk) float mask, 1.0 = masked.  Query i sees key j iff both
+    carry the same non-zero id (and j <= i under `causal`; ids are
+    contiguous, so absolute indices give per-sentence causality).  Rows of
+    id-0 queries come out fully masked."""
+    same = q_seg[:, :, None] == kv_seg[:, None, :]
+    vis = same & (q_seg[:, :, None] != 0)
+    if causal:
+        Sq, Sk = q_seg.shape[1], kv_seg.shape[1]
+        i = torch.arange(Sq, device=q_seg.device)[:, None]
+        j = torch.arange(Sk, device=q_seg.device)[None, :]
+        vis = vis & (j <= i)
+    return (~vis).to(torch.float32)[:, None]
+
+
 # ---------------------------------------------------------------------------
 # K2-K5 / C1 — scaled dot-product attention (reference Attention.py:3-34).
 # q,k,v: (B, H, Sq|Sk, dh); mask broadcastable to (B, H, Sq, Sk), 1.0=masked.
@@ -89,10 +106,14 @@ def residual_layernorm(x, residual, gamma, beta, eps: float = 1e-6):
 # K10 — embedding lookup * sqrt(d) + PE slice (reference Encoder.py:51-53).
 # ---------------------------------------------------------------------------
 
-def embedding_scale_pe(tokens, weight, pe):
-    """tokens (B,S) int64; weight (V,d); pe (1,P,d) with P >= S."""
+def embedding_scale_pe(tokens, weight, pe, positions=None):
+    """tokens (B,S) int64; weight (V,d); pe (1,P,d) with P >= S.
+    positions (B,S) int, optional: PE row per token (packed rows restart the
+    position at every sentence) instead of the token's column."""
     d = weight.shape[1]
     x = F.embedding(tokens, weight) * math.sqrt(d)
+    if positions is not None:
+        return x + pe[0][positions.long()].to(x.dtype)
     return x + pe[:, : tokens.shape[1], :].to(x.dtype)
 
 

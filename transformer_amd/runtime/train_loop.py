@@ -32,7 +32,8 @@ class Train:
                  use_flat: bool | None = None,
                  clip_grad_norm: float = 0.0,
                  skip_nonfinite_grads: bool = False,
-                 grad_accum_steps: int = 1):
+                 grad_accum_steps: int = 1,
+                 pack_sequences: bool = False):
         self.epochs = epochs
         self.enable_function = enable_function
         self.transformer = transformer
@@ -66,6 +67,20 @@ class Train:
                                     if (is_rank0 and test_log_dir) else None)
         self.ckpt_manager = CheckpointManager(transformer, self.optimizer,
                                               ckpt_path, max_ckpt_keep)
+        self.pack_sequences = bool(pack_sequences)
+        if self.pack_sequences:
+            self._refuse_packed_capture()
+
+    _PACKED_CAPTURE_MSG = (
+        "--pack_sequences is not supported together with --enable_function "
+        "(the HIP-graph captured train step has no packed-batch buffers "
+        "yet); run with --noenable_function")
+
+    def _refuse_packed_capture(self):
+        """Packed batches run the eager step only.  Fail loudly — at start-up
+        when the flag is set — instead of falling back silently."""
+        if self._graph_eligible():
+            raise ValueError(self._PACKED_CAPTURE_MSG)
 
     # -- loss (C13, reference train.py:83-88) -------------------------------
     def loss_function(self, real, pred):
@@ -109,13 +124,21 @@ class Train:
             self.train_loss.update(loss)
             self.train_accuracy.update(c / max(t, 1), weight=t)
             return torch.tensor(loss)
+
+        def micro():
+            for i in range(n):
+                s = src[i * rows:(i + 1) * rows]
+                t = tar[i * rows:(i + 1) * rows]
+                if s.shape[0]:
+                    yield ((s, t[:, :-1].contiguous()),
+                           t[:, 1:].contiguous())
+        return self._accum_eager(micro())
+
+    def _accum_eager(self, micro):
+        """Eager accumulation over an iterable of (model input, labels)."""
         sums = None
-        for i in range(n):
-            s, t = src[i * rows:(i + 1) * rows], tar[i * rows:(i + 1) * rows]
-            if s.shape[0] == 0:
-                continue
-            tar_inp, tar_real = t[:, :-1].contiguous(), t[:, 1:].contiguous()
-            predictions, _ = self.transformer((s, tar_inp), training=True)
+        for model_in, tar_real in micro:
+            predictions, _ = self.transformer(model_in, training=True)
             loss = self.loss_function(tar_real, predictions)
             # per micro-batch: the embedding scatter and the column-sum
             # reductions accumulate into flat_g and need it clear
@@ -152,7 +175,34 @@ class Train:
         self.train_accuracy.update(c / max(t, 1), weight=t)
         return loss
 
+    def _packed_train_step(self, pb):
+        """train_step on a PackedBatch: the same loss_function with the same
+        GLOBAL batch divisor over the packed (rows, L) logits and labels —
+        the pad mask of the CE and of the accuracy drops id-0 slots — and
+        the same optimizer step.  Gradient accumulation chunks ROWS."""
+        self._refuse_packed_capture()
+        n = self.grad_accum_steps
+        if n > 1:
+            rows = -(-pb.src.shape[0] // n)
+            return self._accum_eager(
+                (c, c.tar_real) for c in
+                (pb.rows(i * rows, (i + 1) * rows) for i in range(n))
+                if c.src.shape[0])
+        predictions, _ = self.transformer(pb, training=True)
+        loss = self.loss_function(pb.tar_real, predictions)
+        self.optimizer.zero_grad()
+        loss.backward()
+        self._grad_sync()
+        self.optimizer.step()
+        self.train_loss.update(loss.detach().item())
+        c, t = ops.masked_accuracy_counts(predictions.detach(), pb.tar_real)
+        self.train_accuracy.update(c / max(t, 1), weight=t)
+        return loss
+
     def train_step(self, inputs):
+        if hasattr(inputs, "src_seg"):      # data.PackedBatch
+            return self._packed_train_step(
+                inputs.to(self.device, non_blocking=True))
         src, tar = inputs
         src = src.to(self.device, non_blocking=True)
         tar = tar.to(self.device, non_blocking=True)
@@ -297,8 +347,13 @@ class Train:
             interval_tokens = 0
             interval_t0 = time.time()
             for inputs in train_dataset:
-                src, tar = inputs
-                interval_tokens += src.numel() + tar.numel()
+                if hasattr(inputs, "src_seg"):
+                    # packed: count REAL tokens (a padded batch counts its
+                    # slots, as before)
+                    interval_tokens += inputs.real_tokens()
+                else:
+                    src, tar = inputs
+                    interval_tokens += src.numel() + tar.numel()
                 self.train_step(inputs)
                 step += 1
                 if self._stop_requested:
