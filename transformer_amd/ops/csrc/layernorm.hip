@@ -72,7 +72,9 @@ void ln_fwd_kernel(const short* __restrict__ x, const short* __restrict__ res,
       }
       *(s16x8*)(s + base + c) = sv;
     } else {
-      for (int j = 0; c + j < D; ++j) {
+      // scalar path: the lane still owns columns [c, c+8) only — running
+      // on to D would add its neighbours' columns to the row sums again
+      for (int j = 0; j < 8 && c + j < D; ++j) {
         float xj = bfbits2f(x[base + c + j]);
         if (DROP) {
           unsigned char keep =
@@ -109,7 +111,7 @@ void ln_fwd_kernel(const short* __restrict__ x, const short* __restrict__ res,
                          bfbits2f(bv[j]));
       *(s16x8*)(y + base + c) = yv;
     } else {
-      for (int j = 0; c + j < D; ++j)
+      for (int j = 0; j < 8 && c + j < D; ++j)
         y[base + c + j] =
             f2bfbits((bfbits2f(s[base + c + j]) - mean) * rstd *
                          bfbits2f(gamma[c + j]) + bfbits2f(beta[c + j]));
@@ -151,7 +153,7 @@ void ln_bwd_kernel(const short* __restrict__ dy, const short* __restrict__ s,
         sgx += g * xh;
       }
     } else {
-      for (int j = 0; c + j < D; ++j) {
+      for (int j = 0; j < 8 && c + j < D; ++j) {
         float xh = (bfbits2f(s[base + c + j]) - mu) * rs;
         float g = bfbits2f(dy[base + c + j]) * bfbits2f(gamma[c + j]);
         sg += g;
@@ -182,7 +184,7 @@ void ln_bwd_kernel(const short* __restrict__ dy, const short* __restrict__ s,
       *(s16x8*)(dx + base + c) = xo;
       if (DROP) *(s16x8*)(dxm + base + c) = mo;
     } else {
-      for (int j = 0; c + j < D; ++j) {
+      for (int j = 0; j < 8 && c + j < D; ++j) {
         float xh = (bfbits2f(s[base + c + j]) - mu) * rs;
         float g = bfbits2f(dy[base + c + j]) * bfbits2f(gamma[c + j]);
         float d = rs * (g - sg - xh * sgx);
