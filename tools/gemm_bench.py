@@ -6,8 +6,25 @@ For each backward shape it times BOTH implementations:
   dX:  gemm_nn(dy, w)            vs  transpose2d(w) + gemm_nt(dy, wT)
   dW:  gemm_tn(dy, x)            vs  transpose2d(dy)+transpose2d(x)+gemm_nt
 so the functional layer's dispatch choices are measurement-driven.
+
+gemm256 epilogue arms (TFMX_G256_EPI, read per call), device events, arms
+interleaved round-robin in one process, one JSON line per result:
+
+    python tools/gemm_bench.py --ksweep [rounds] [iters]
+        gemm256_nt at the QKV / attn-O / FFN1 / logits forward (M, N) for
+        K = 128..2048 per arm, and the line fit  us = fixed + slope * K/64
+        (fixed = per-call prologue + epilogue, slope = one K-tile).
+    python tools/gemm_bench.py --epi [rounds] [iters]
+        scalar vs vec8 vs lds at the seven forward and five dX shapes
+        (dX as the trainer runs it: NT against the transposed weight).
+    python tools/gemm_bench.py --ffn [rounds] [iters]
+        FFN2 dX + relu_bwd and FFN1 dX + add at M=16384: GEMM + separate
+        pass vs the fused relu-mask / residual-add epilogue, per arm.
 """
 
+import json
+import os
+import statistics
 import sys
 import time
 
@@ -58,7 +75,120 @@ DW = [
 ]
 
 
+EPI_ARMS = ("scalar", "vec8", "lds")
+
+
+def _with_arm(arm, fn):
+    def run():
+        os.environ["TFMX_G256_EPI"] = arm
+        fn()
+    return run
+
+
+def time_arms(arms, rounds, iters, warmup=3):
+    """{name: us/call stats}; arms take turns inside every round."""
+    for fn in arms.values():
+        for _ in range(warmup):
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in arms}
+    for _ in range(rounds):
+        for name, fn in arms.items():
+            a = torch.cuda.Event(enable_timing=True)
+            b = torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(iters):
+                fn()
+            b.record()
+            b.synchronize()
+            times[name].append(a.elapsed_time(b) * 1e3 / iters)
+    os.environ.pop("TFMX_G256_EPI", None)
+    return {k: {"median_us": round(statistics.median(v), 2),
+                "min_us": round(min(v), 2), "max_us": round(max(v), 2)}
+            for k, v in times.items()}
+
+
+def _rb(*shape):
+    return torch.randn(*shape, device="cuda", dtype=torch.bfloat16)
+
+
+def ksweep(rounds, iters):
+    import numpy as np
+    E = ext()
+    ks = (128, 256, 512, 1024, 2048)
+    for (m, n, _, tag) in (FWD[0], FWD[1], FWD[2], FWD[4]):
+        bias = _rb(n)
+        out = torch.empty(m, n, device="cuda", dtype=torch.bfloat16)
+        ops = {k: (_rb(m, k), _rb(n, k)) for k in ks}
+        arms = {}
+        for k in ks:
+            a, w = ops[k]
+            for arm in EPI_ARMS:
+                arms[f"{arm}:{k}"] = _with_arm(
+                    arm, lambda a=a, w=w: E.gemm256_nt(a, w, bias, 0, out))
+        res = time_arms(arms, rounds, iters)
+        for arm in EPI_ARMS:
+            us = [res[f"{arm}:{k}"]["median_us"] for k in ks]
+            slope, fixed = np.polyfit([k / 64 for k in ks], us, 1)
+            print(json.dumps({
+                "bench": "ksweep", "shape": tag, "M": m, "N": n, "arm": arm,
+                "us_by_K": dict(zip(ks, us)),
+                "fixed_us": round(float(fixed), 2),
+                "us_per_ktile": round(float(slope), 3),
+                "fixed_share_at_K512": round(
+                    float(fixed) / res[f"{arm}:512"]["median_us"], 3),
+            }), flush=True)
+
+
+def epi_arms(rounds, iters):
+    E = ext()
+    cases = [(m, n, k, tag, True) for (m, n, k, tag) in FWD]
+    for (m, n_out, k_in, tag) in DX:
+        # the head's dY arrives zero-padded to a multiple of 256 columns
+        kc = (n_out + 255) // 256 * 256 if n_out % 64 else n_out
+        cases.append((m, k_in, kc, tag, False))
+    for (m, n, k, tag, has_bias) in cases:
+        a, w = _rb(m, k), _rb(n, k)
+        bias = _rb(n) if has_bias else torch.Tensor()
+        out = torch.empty(m, n, device="cuda", dtype=torch.bfloat16)
+        on256 = bool(E.gemm256_viable(m, n, k))
+        arms = {arm: _with_arm(arm, lambda: E.gemm_nt(a, w, bias, 0))
+                for arm in EPI_ARMS}
+        res = time_arms(arms, rounds, iters)
+        print(json.dumps({"bench": "epi", "shape": tag, "M": m, "N": n,
+                          "K": k, "gemm256": on256, "times": res}),
+              flush=True)
+        del a, w, out
+
+
+def ffn_fused(rounds, iters):
+    E = ext()
+    m, d, dff = 16384, 512, 2048
+    nob = torch.Tensor()
+    dxm, w2t, h = _rb(m, d), _rb(dff, d), torch.relu(_rb(m, dff))
+    dz, w1t, dres = _rb(m, dff), _rb(d, dff), _rb(m, d)
+    arms = {}
+    for arm in EPI_ARMS:
+        arms[f"ffn2_split:{arm}"] = _with_arm(
+            arm, lambda: E.relu_bwd(E.gemm_nt(dxm, w2t, nob, 0), h))
+        arms[f"ffn2_fused:{arm}"] = _with_arm(
+            arm, lambda: E.gemm256_nt(dxm, w2t, nob, 2, None, h))
+        arms[f"ffn1_split:{arm}"] = _with_arm(
+            arm, lambda: E.gemm_nt(dz, w1t, nob, 0) + dres)
+        arms[f"ffn1_fused:{arm}"] = _with_arm(
+            arm, lambda: E.gemm256_nt(dz, w1t, nob, 3, None, dres))
+    res = time_arms(arms, rounds, iters)
+    print(json.dumps({"bench": "ffn", "M": m, "times": res}), flush=True)
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] in ("--ksweep", "--epi", "--ffn"):
+        rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+        iters = int(sys.argv[3]) if len(sys.argv) > 3 else 20
+        torch.manual_seed(0)
+        {"--ksweep": ksweep, "--epi": epi_arms,
+         "--ffn": ffn_fused}[sys.argv[1]](rounds, iters)
+        return
     iters = int(sys.argv[1]) if len(sys.argv) > 1 else 20
     E = ext()
     torch.manual_seed(0)

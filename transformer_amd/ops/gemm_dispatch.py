@@ -244,9 +244,11 @@ def _dx_epilogue_ok(E, M, n_out, k):
     """Whether the dX GEMM (M, n_out, k) would run on the gemm256 kernel —
     the only one carrying the relu-mask / residual-add epilogues — through
     the cached-W^T backend.  Opt-in, TFMX_FFN_BWD=fused (A/B arm, read per
-    call): with the aux tensor read in the epilogue's 2-byte store pattern
-    behind a 1-block/CU main loop, both fused GEMMs measured SLOWER than
-    GEMM + separate pass (docs/PERF.md), so the default stays split."""
+    call).  Since the epilogue reads aux in 8/16-byte row-contiguous pieces
+    both fused GEMMs beat GEMM + separate pass per op (docs/PERF.md); the
+    default is still split because tests/test_gpu_fused_backward.py pins
+    the unset arm to two _dx_gemm calls — flipping it goes with a rewrite
+    of that test."""
     return (os.environ.get("TFMX_FFN_BWD", "split") == "fused"
             and _DX_BACKEND == "wt" and M >= 2048
             and n_out % 64 == 0 and k % 64 == 0
