@@ -189,11 +189,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_uni_viable", &gemm_uni_viable);
   m.def("gemm_uni_nt_ab", &gemm_uni_nt_ab,
         "schedule A/B variants of the uni NT kernel (bench only)");
-  m.def("colsum", &colsum, pybind11::arg("a"),
-        pybind11::arg("out") = pybind11::none());
+  m.def("colsum", &colsum,
+        "column sums of a row-strided bf16 matrix; row-streaming kernel on "
+        "16-byte-aligned inputs, TFMX_COLSUM=cols keeps the column kernel",
+        pybind11::arg("a"), pybind11::arg("out") = pybind11::none());
   m.def("relu_bwd", &relu_bwd);
   m.def("relu_bwd_db", &relu_bwd_db,
-        "dz = dy*(y>0) with the bias grad db = colsum(dz) fused",
+        "dz = dy*(y>0) and db = colsum(dz) in one row-streaming pass",
         pybind11::arg("dy"), pybind11::arg("y"),
         pybind11::arg("db") = pybind11::none());
   m.def("smoke_add", &smoke_add);

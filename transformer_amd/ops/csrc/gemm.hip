@@ -19,6 +19,8 @@
 // remap for L2 affinity (8 XCDs with private L2s).
 #include "common.h"
 
+#include <cstdint>
+#include <cstring>
 #include <map>
 
 #include <torch/extension.h>
@@ -374,6 +376,10 @@ void transpose_batch_kernel(const long* __restrict__ desc) {
 }
 
 // colsum: db[N] = sum_m dy[M,N] (fp32 accumulate, bf16 out).
+// colsum_kernel is the column-parallel form: one thread per column, 2-byte
+// loads.  It runs where colsum_rows_kernel (below) cannot — rows that are
+// not 16-byte aligned —, below 512 columns, and as the TFMX_COLSUM=cols
+// A/B arm.
 // Two-stage: (col-chunk, row-chunk) blocks fill the chip, fp32 atomics
 // into a workspace, then cast.  The workspace is CACHED per (device, N)
 // and re-zeroed by the cast kernel, so the zero-fill launch happens once
@@ -414,59 +420,140 @@ void colsum_kernel(const short* __restrict__ dy, float* __restrict__ acc,
   }
 }
 
-// relu_bwd fused with the bias grad: dz = dy * (y > 0), db = colsum(dz).
-// Column-parallel layout (thread = column, row loop — the same coalesced
-// pattern as colsum_kernel) so the separate colsum pass's full re-read of
-// dz (64 MB per FFN1 backward) disappears; finalize via last-arriver.
-#define RELU_ROWS 64
-__global__ __launch_bounds__(256)
-void relu_bwd_db_kernel(const short* __restrict__ dy,
-                        const short* __restrict__ y,
-                        short* __restrict__ dz, float* __restrict__ acc,
-                        short* __restrict__ db, int M, int N) {
-  // 8 adjacent columns per thread with s16x8 loads/stores (scalar
-  // column loads measured 2.3x off roofline), 8 fp32 accumulators,
-  // 8 atomics per thread at the end.
-  const int n8 = (blockIdx.x * 256 + threadIdx.x) * 8;
-  if (n8 + 8 <= N) {
-    long m0 = (long)blockIdx.y * RELU_ROWS;
-    long m1 = min((long)M, m0 + RELU_ROWS);
-    float sc[8] = {0.f};
-    for (long m = m0; m < m1; ++m) {
-      s16x8 dv = *(const s16x8*)(dy + m * N + n8);
-      s16x8 yv = *(const s16x8*)(y + m * N + n8);
-      s16x8 o;
+// Row-streaming column sum (the ln_bwd_fused_kernel recipe): a lane owns 8
+// adjacent columns per 512-column chunk (c = panel + k*512 + lane*8, one
+// 16-byte load each) and keeps their sums in fp32 registers while the
+// block's waves walk the rows grid-stride, the next row's loads issued
+// before this row's adds.  Grid: x = column panels of NCH chunks, y = row
+// groups of NW waves.  A block combines its waves by a register tree
+// through LDS (index c + c/8, no LDS atomics), adds ONE fp32 atomic per
+// column into the cached workspace (start segment rotated by row group),
+// and the last arriver casts to bf16 and re-zeroes: same workspace
+// contract as colsum_kernel.  Needs dy 16-byte aligned and lda % 8 == 0;
+// the 8-column group that crosses N (at most one lane per row) is read by
+// guarded scalar loads, so nothing past (M-1)*lda + N - 1 is touched.
+// RELU: y and dz are (M, N) with the same lda; writes dz = y > 0 ? dy : 0
+// (relu_bwd_kernel's predicate and bits) and sums the written value.
+template <bool RELU, int NCH, int NW>
+__global__ __launch_bounds__(NW * 64)
+void colsum_rows_kernel(const short* __restrict__ dy,
+                        const short* __restrict__ y, short* __restrict__ dz,
+                        float* __restrict__ acc, short* __restrict__ out,
+                        int M, int N, long lda) {
+  constexpr int LW = NCH * 576;  // one wave's accumulators, padded
+  __shared__ float red[(NW / 2) * LW];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int panel = blockIdx.x * (NCH * WAVE * 8);
+
+  int nv[NCH];  // valid columns of the lane's group: 8, 1..7 (tail) or 0
+  float a[NCH][8];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        o[j] = (bfbits2f(yv[j]) > 0.f) ? dv[j] : (short)0;
-        sc[j] += bfbits2f(o[j]);
-      }
-      *(s16x8*)(dz + m * N + n8) = o;
+  for (int k = 0; k < NCH; ++k) {
+    const int c = panel + k * (WAVE * 8) + lane * 8;
+    nv[k] = min(8, max(0, N - c));
+#pragma unroll
+    for (int j = 0; j < 8; ++j) a[k][j] = 0.f;
+  }
+
+  auto load8 = [&](const short* __restrict__ p, int n) {
+    s16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (n == 8) {
+      v = *(const s16x8*)p;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 7; ++j)
+        if (j < n) v[j] = p[j];
     }
+    return v;
+  };
+  s16x8 dv[NCH], yv[NCH], dvn[NCH], yvn[NCH];
+  auto load_row = [&](int row, s16x8 (&d)[NCH], s16x8 (&x)[NCH]) {
+    const long base = (long)row * lda + panel + lane * 8;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) atomicAdd(&acc[n8 + j], sc[j]);
-  } else if (n8 < N) {
-    long m0 = (long)blockIdx.y * RELU_ROWS;
-    long m1 = min((long)M, m0 + RELU_ROWS);
-    for (int j = 0; n8 + j < N; ++j) {
-      float sc = 0.f;
-      for (long m = m0; m < m1; ++m) {
-        short a = (bfbits2f(y[m * N + n8 + j]) > 0.f) ? dy[m * N + n8 + j]
-                                                      : (short)0;
-        dz[m * N + n8 + j] = a;
-        sc += bfbits2f(a);
+    for (int k = 0; k < NCH; ++k) {
+      d[k] = load8(dy + base + k * (WAVE * 8), nv[k]);
+      if (RELU) x[k] = load8(y + base + k * (WAVE * 8), nv[k]);
+    }
+  };
+  const int row0 = blockIdx.y * NW + wave, rstep = gridDim.y * NW;
+  if (row0 < M) load_row(row0, dvn, yvn);
+  for (int row = row0; row < M; row += rstep) {
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+      dv[k] = dvn[k];
+      if (RELU) yv[k] = yvn[k];
+    }
+    if (row + rstep < M) load_row(row + rstep, dvn, yvn);
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+      if (RELU) {
+        s16x8 o;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          o[j] = (bfbits2f(yv[k][j]) > 0.f) ? dv[k][j] : (short)0;
+        short* q = dz + (long)row * lda + panel + k * (WAVE * 8) + lane * 8;
+        if (nv[k] == 8) {
+          *(s16x8*)q = o;
+        } else {
+#pragma unroll
+          for (int j = 0; j < 7; ++j)
+            if (j < nv[k]) q[j] = o[j];
+        }
+        dv[k] = o;
       }
-      atomicAdd(&acc[n8 + j], sc);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) a[k][j] += bfbits2f(dv[k][j]);
     }
   }
-  if (last_arriver((unsigned*)(acc + N), gridDim.x * gridDim.y)) {
-    for (int i = threadIdx.x; i < N; i += 256) {
-      db[i] = f2bfbits(acc[i]);
+
+  // Block combine: binary tree over the waves, registers to registers (the
+  // upper half of the live waves parks, the lower half adds).
+  auto park = [&](float* dst) {
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+      if (nv[k] > 0) {
+        const int li = (lane + k * WAVE) * 9;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) dst[li + j] = a[k][j];
+      }
+    }
+  };
+#pragma unroll
+  for (int half = NW / 2; half >= 1; half >>= 1) {
+    if (wave >= half && wave < 2 * half) park(red + (wave - half) * LW);
+    __syncthreads();
+    if (wave < half) {
+      const float* src = red + wave * LW;
+#pragma unroll
+      for (int k = 0; k < NCH; ++k) {
+        if (nv[k] > 0) {
+          const int li = (lane + k * WAVE) * 9;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) a[k][j] += src[li + j];
+        }
+      }
+    }
+    __syncthreads();
+  }
+  if (wave == 0) park(red);
+  __syncthreads();
+  // cross-block: one fp32 atomic per column of the panel per block
+  const int pw = min(NCH * WAVE * 8, N - panel);
+  const int rot = (int)((blockIdx.y * 64u) % (unsigned)pw);
+  for (int i = threadIdx.x; i < pw; i += NW * 64) {
+    int c = i + rot;
+    if (c >= pw) c -= pw;
+    atomicAdd(&acc[panel + c], red[c + (c >> 3)]);
+  }
+  unsigned* cnt = (unsigned*)(acc + N);
+  if (last_arriver(cnt, gridDim.x * gridDim.y)) {
+    for (int i = threadIdx.x; i < N; i += NW * 64) {
+      out[i] = f2bfbits(acc[i]);
       acc[i] = 0.f;
     }
     if (threadIdx.x == 0)
-      __hip_atomic_store((unsigned*)(acc + N), 0u, __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
@@ -669,63 +756,107 @@ void transpose_batch(torch::Tensor desc) {
       desc.data_ptr<long>());
 }
 
+// Cached fp32 workspace (N floats + the arrival counter) per (device, N),
+// shared by colsum_kernel and both colsum_rows_kernel forms: each finds
+// it zero and leaves it zero.
+static float* colsum_ws(const torch::Tensor& like, int N) {
+  static std::map<std::pair<int, int>, torch::Tensor> ws_cache;
+  auto key = std::make_pair((int)like.get_device(), N);
+  auto it = ws_cache.find(key);
+  if (it == ws_cache.end())
+    it = ws_cache.emplace(key, torch::zeros(
+        {N + 1}, like.options().dtype(torch::kFloat32))).first;  // +counter
+  return it->second.data_ptr<float>();
+}
+
+static torch::Tensor colsum_dest(c10::optional<torch::Tensor>& o,
+                                 const torch::Tensor& like, int N) {
+  if (!o.has_value()) return torch::empty({N}, like.options());
+  TORCH_CHECK(o->is_cuda() && o->dtype() == torch::kBFloat16 &&
+              o->is_contiguous() && o->numel() == N, "colsum: bad out");
+  return *o;
+}
+
+// The row kernel's loads are 16 bytes wide.  TFMX_COLSUM (A/B arms, read
+// per call): cols keeps colsum_kernel everywhere, rows takes the row
+// kernel wherever its loads are possible.  Unset, a plain colsum narrower
+// than one 512-column chunk keeps colsum_kernel: with part of every wave
+// idle the row kernel measured no faster there (N = 64 and 192 against
+// 512, docs/PERF.md).  relu_bwd_db asks with narrow_ok: its one pass
+// replaces two at any width.
+static bool colsum_rows_ok(const void* p, long lda, bool narrow_ok) {
+  const char* arm = getenv("TFMX_COLSUM");
+  if (arm && strcmp(arm, "cols") == 0) return false;
+  if (((uintptr_t)p & 15) != 0 || lda % 8 != 0) return false;
+  return narrow_ok || (arm && strcmp(arm, "rows") == 0);
+}
+
+#define CSR_NW 8  // waves per block of colsum_rows_kernel
+// Panels of 1, 2 or 4 chunks (N <= 2048, <= 8192, wider).  Row groups: two
+// blocks per CU over all panels, but at least COLSUM_ROWS rows per block,
+// so a column never takes more atomics (and their order is never a larger
+// share of the rounding) than with colsum_kernel.
+template <bool RELU>
+static void colsum_rows_launch(const short* dy, const short* y, short* dz,
+                               float* acc, short* out, int M, int N,
+                               long lda, hipStream_t stream) {
+  const int nch = N <= 2048 ? 1 : N <= 8192 ? 2 : 4;
+  const int panels = cdiv(N, nch * 512);
+  const int cus = at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+  const int groups = std::max(1, std::min(cdiv(M, COLSUM_ROWS),
+                                          cdiv(2 * cus, panels)));
+  dim3 grid(panels, groups);
+  auto launch = [&](auto nchc) {
+    constexpr int NCH = decltype(nchc)::value;
+    colsum_rows_kernel<RELU, NCH, CSR_NW><<<grid, CSR_NW * 64, 0, stream>>>(
+        dy, y, dz, acc, out, M, N, lda);
+  };
+  if (nch == 1) launch(std::integral_constant<int, 1>{});
+  else if (nch == 2) launch(std::integral_constant<int, 2>{});
+  else launch(std::integral_constant<int, 4>{});
+}
+
 torch::Tensor colsum(torch::Tensor a, c10::optional<torch::Tensor> out_opt) {
   TORCH_CHECK(a.is_cuda() && a.dtype() == torch::kBFloat16 && a.dim() == 2 &&
               a.stride(1) == 1, "colsum: bad a");
   int M = a.size(0), N = a.size(1);
   const long lda = a.stride(0);
-  static std::map<std::pair<int, int>, torch::Tensor> ws_cache;
-  auto key = std::make_pair((int)a.get_device(), N);
-  auto it = ws_cache.find(key);
-  if (it == ws_cache.end())
-    it = ws_cache.emplace(key, torch::zeros(
-        {N + 1}, a.options().dtype(torch::kFloat32))).first;  // +counter
-  torch::Tensor acc = it->second;
-  torch::Tensor out;
-  if (out_opt.has_value()) {
-    out = *out_opt;
-    TORCH_CHECK(out.is_cuda() && out.dtype() == torch::kBFloat16 &&
-                out.is_contiguous() && out.numel() == N);
-  } else {
-    out = torch::empty({N}, a.options());
-  }
+  float* acc = colsum_ws(a, N);
+  torch::Tensor out = colsum_dest(out_opt, a, N);
   auto stream = at::hip::getCurrentHIPStream();
+  if (M > 0 && N > 0 && colsum_rows_ok(a.data_ptr(), lda, N >= 512)) {
+    colsum_rows_launch<false>((const short*)a.data_ptr(), nullptr, nullptr,
+                              acc, (short*)out.data_ptr(), M, N, lda, stream);
+    return out;
+  }
   dim3 grid(cdiv(N, 256), cdiv(M, COLSUM_ROWS));
   colsum_kernel<<<grid, 256, 0, stream>>>(
-      (const short*)a.data_ptr(), acc.data_ptr<float>(),
-      (short*)out.data_ptr(), M, N, lda);
+      (const short*)a.data_ptr(), acc, (short*)out.data_ptr(), M, N, lda);
   return out;
 }
 
-// Fused variant: returns (dz, db).  Reuses colsum's cached fp32
-// workspace (N floats + counter) keyed per (device, N).
+torch::Tensor relu_bwd(torch::Tensor dy, torch::Tensor y);
+
+// (dz, db) = (dy * (y > 0), colsum(dz)): the row kernel writes dz while it
+// sums it, so dz is not read back.  Shapes its 16-byte path cannot take
+// (N % 8 != 0, misaligned) run relu_bwd + colsum.
 std::vector<torch::Tensor> relu_bwd_db(torch::Tensor dy, torch::Tensor y,
                                        c10::optional<torch::Tensor> db_out) {
   TORCH_CHECK(dy.is_cuda() && dy.dtype() == torch::kBFloat16 &&
               dy.dim() == 2 && dy.is_contiguous() && y.is_contiguous() &&
               y.sizes() == dy.sizes(), "relu_bwd_db: bad inputs");
   const int M = dy.size(0), N = dy.size(1);
-  auto dz = torch::empty_like(dy);
-  torch::Tensor db;
-  if (db_out.has_value()) {
-    db = *db_out;
-    TORCH_CHECK(db.is_cuda() && db.dtype() == torch::kBFloat16 &&
-                db.is_contiguous() && db.numel() == N);
-  } else {
-    db = torch::empty({N}, dy.options());
+  if (!(M > 0 && N > 0 && colsum_rows_ok(dy.data_ptr(), N, true) &&
+        ((uintptr_t)y.data_ptr() & 15) == 0)) {
+    auto dz = relu_bwd(dy, y);
+    return {dz, colsum(dz, db_out)};
   }
-  static std::map<std::pair<int, int>, torch::Tensor> ws_cache;
-  auto key = std::make_pair((int)dy.get_device(), N);
-  auto it = ws_cache.find(key);
-  if (it == ws_cache.end())
-    it = ws_cache.emplace(key, torch::zeros(
-        {N + 1}, dy.options().dtype(torch::kFloat32))).first;
-  auto stream = at::hip::getCurrentHIPStream();
-  dim3 grid(cdiv(N, 256 * 8), cdiv(M, RELU_ROWS));
-  relu_bwd_db_kernel<<<grid, 256, 0, stream>>>(
+  auto dz = torch::empty_like(dy);
+  torch::Tensor db = colsum_dest(db_out, dy, N);
+  colsum_rows_launch<true>(
       (const short*)dy.data_ptr(), (const short*)y.data_ptr(),
-      (short*)dz.data_ptr(), it->second.data_ptr<float>(),
-      (short*)db.data_ptr(), M, N);
+      (short*)dz.data_ptr(), colsum_ws(dy, N), (short*)db.data_ptr(), M, N,
+      N, at::hip::getCurrentHIPStream());
   return {dz, db};
 }
 

@@ -156,18 +156,19 @@ class _LinearFn(torch.autograd.Function):
         x, y = ctx.saved_tensors
         w, b = ctx.params
         flat = ctx.flat
-        if ctx.activation == "relu":
-            # (A fused relu+colsum kernel — relu_bwd_db — was built and
-            # measured SLOWER in context at every grid shape: the column-
-            # parallel layout + per-column atomics lose to the flat
-            # 16k-block stream + separate colsum, the same result as
-            # round 1's column-reduction experiments.  docs/PERF.md.)
+        db = None
+        if ctx.activation == "relu" and b is not None:
+            # dz = dy * (y > 0) and db = colsum(dz) in one row-streaming
+            # pass: the kernel that writes dz carries its column sums, so
+            # dz is not read a second time for the bias gradient.
+            dy, db = E.relu_bwd_db(dy.contiguous(), y, _grad_dst(b, flat))
+        elif ctx.activation == "relu":
             dy = E.relu_bwd(dy.contiguous(), y)  # dz = dy * (y > 0)
         else:
             dy = _dense2d(dy)
         dx = _dx_gemm(E, dy, w)         # dX[M,K] = dY[M,N] @ W[N,K]
         dw, db = _dw_db_gemm(dy, x, b is not None, w_out=_grad_dst(w, flat),
-                             b_out=_grad_dst(b, flat))
+                             b_out=_grad_dst(b, flat), db=db)
         if flat:
             _grad_ready(w, b)
             dw = db = None
@@ -524,10 +525,16 @@ class _FFNDropLNFn(torch.autograd.Function):
         if _dx_epilogue_ok(E, M, dff, d):
             # dz = (dxm @ W2) * (h > 0), mask applied on the accumulators
             dz = E.gemm256_nt(dxm, _wt_padded(E, w2), nob, 2, None, h)
+            db1 = E.colsum(dz, _grad_dst(b1, flat)) if b1 is not None \
+                else None
+        elif b1 is not None:
+            # the pass that writes dz also sums it: no colsum re-read
+            dz, db1 = E.relu_bwd_db(_dx_gemm(E, dxm, w2).contiguous(), h,
+                                    _grad_dst(b1, flat))
         else:
             dz = E.relu_bwd(_dx_gemm(E, dxm, w2).contiguous(), h)
+            db1 = None
         dw1 = _dw_gemm(dz, x, out=_grad_dst(w1, flat))
-        db1 = E.colsum(dz, _grad_dst(b1, flat)) if b1 is not None else None
         if flat:
             _grad_ready(w1, b1)
             dw1 = db1 = dw2 = db2 = dg = dbt = None

@@ -193,14 +193,17 @@ def _dw_gemm(dy, x, out=None):
     return E.gemm_dw(dy.contiguous(), x, out, None, None)
 
 
-def _dw_db_gemm(dy, x, has_bias, w_out=None, b_out=None):
+def _dw_db_gemm(dy, x, has_bias, w_out=None, b_out=None, db=None):
     """dW and (optionally) db together.  gemm_dw CAN fuse db into its dY
     stream, but the fused variant costs 138 vs 116 VGPRs — one whole
     workgroup of block-level overlap per CU — and measured slower
-    end-to-end than a separate colsum pass, so db stays separate."""
+    end-to-end than a separate colsum pass, so db is a pass of its own
+    (the row-streaming colsum) unless the caller hands in a finished
+    `db`: the relu backward sums dz in the kernel that writes it."""
     E = ext()
     dw = _dw_gemm(dy, x, out=w_out)
-    db = E.colsum(dy, b_out) if has_bias else None
+    if db is None and has_bias:
+        db = E.colsum(dy, b_out)
     return dw, db
 
 
