@@ -3,7 +3,8 @@ the reference exports a SavedModel for serving, train.py:246 — this is the
 serving side of that capability).
 
     python serve.py --model_dir model --src_vocab src_vocab.txt \
-        --tgt_vocab tgt_vocab.txt [--device cuda] [--port 8000]
+        --tgt_vocab tgt_vocab.txt [--device cuda] [--port 8000] \
+        [--fused_decode_attn]
 
 Endpoints:
     GET  /health               -> {"status": "ok", "config": {...}}
@@ -28,7 +29,8 @@ import torch
 
 
 def build_app(model_dir: str, src_vocab: str, tgt_vocab: str,
-              device: str = "cpu", dtype=None):
+              device: str = "cpu", dtype=None,
+              fused_decode_attn: bool = False):
     from fastapi import Body, FastAPI
 
     from transformer_amd.runtime.export import load_exported
@@ -66,7 +68,8 @@ def build_app(model_dir: str, src_vocab: str, tgt_vocab: str,
             graphed[key] = GraphedDecoder(
                 model, B=1, S_src=key[0], max_len=key[1],
                 start_id=tgt_tok.vocab_size,
-                device=next(model.parameters()).device)
+                device=next(model.parameters()).device,
+                fused_attn=fused_decode_attn)
         return graphed[key], key[0]
 
     app = FastAPI(title="transformer_amd", version="1.0")
@@ -97,7 +100,8 @@ def build_app(model_dir: str, src_vocab: str, tgt_vocab: str,
                     out = dec(padded, tgt_start + 1, max_len=max_len)
             else:
                 out = greedy_decode(model, enc_in, tgt_start, tgt_start + 1,
-                                    max_len=max_len)
+                                    max_len=max_len,
+                                    fused_attn=fused_decode_attn)
         ids = out.squeeze(0).tolist()
         body = [t for t in ids if 0 < t < tgt_tok.vocab_size]
         return {"tokens": ids, "text": tgt_tok.decode(body)}
@@ -114,12 +118,16 @@ def main(argv=None):
                    default="cuda" if torch.cuda.is_available() else "cpu")
     p.add_argument("--host", type=str, default="127.0.0.1")
     p.add_argument("--port", type=int, default=8000)
+    p.add_argument("--fused_decode_attn", action="store_true",
+                   help="decode with the single-query split-KV attention "
+                        "kernels (fused KV append); off by default")
     args = p.parse_args(argv)
 
     import uvicorn
     app = build_app(args.model_dir, args.src_vocab, args.tgt_vocab,
                     args.device,
-                    torch.bfloat16 if args.device.startswith("cuda") else None)
+                    torch.bfloat16 if args.device.startswith("cuda") else None,
+                    fused_decode_attn=args.fused_decode_attn)
     uvicorn.run(app, host=args.host, port=args.port)
 
 

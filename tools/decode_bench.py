@@ -1,10 +1,20 @@
-"""Serving decode latency: eager KV-cached loop vs hipGraph-captured decoder.
+"""Serving decode latency: eager KV-cached loop vs hipGraph-captured decoder
+vs the captured decoder on the single-query decode-attention kernels.
 
 Transformer-base, greedy decode.  The eager loop is launch-bound at small
 batch (hundreds of kernel launches per token); GraphedDecoder replays one
-captured graph per token.
+captured graph per token; with fused_attn=True each attention of the
+captured step is one split-KV launch that also appends the K/V row.
+
+    python tools/decode_bench.py [--reps N] [--long] [--no_eager]
+
+--reps N  time each graphed decoder N times, alternating the two, and print
+          the median and the min..max spread of ms/token
+--long    add the long-context point B=1, S_src=64, L=2048
 """
+import argparse
 import os
+import statistics
 import sys
 import time
 
@@ -14,43 +24,72 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from transformer_amd.models import Transformer
 from transformer_amd.models.transformer import GraphedDecoder, greedy_decode
 
+ap = argparse.ArgumentParser()
+ap.add_argument("--reps", type=int, default=1)
+ap.add_argument("--long", action="store_true")
+ap.add_argument("--no_eager", action="store_true")
+args = ap.parse_args()
+
+START, END = 32768, 32769
 torch.manual_seed(0)
 m = Transformer(num_layers=6, d_model=512, num_heads=8, dff=2048,
                 input_vocab_size=32770, target_vocab_size=32770,
                 rate=0.0, max_position=4096).cuda().bfloat16()
 m.eval()
 
-for B, S, L in [(1, 64, 256), (8, 64, 256), (16, 128, 128), (64, 256, 64)]:
+
+def timed(fn):
+    torch.cuda.synchronize(); t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return out, time.perf_counter() - t0
+
+
+def same_until_end(a, b):
+    for ra, rb in zip(a.tolist(), b.tolist()):
+        for x, y in zip(ra, rb):
+            if x != y:
+                return False
+            if x == END:
+                break
+    return True
+
+
+def stats(ts, L):
+    ms = [t * 1e3 / L for t in ts]
+    return f"{statistics.median(ms):.3f} [{min(ms):.3f}..{max(ms):.3f}]"
+
+
+configs = [(1, 64, 256), (8, 64, 256), (16, 128, 128), (64, 256, 64)]
+if args.long:
+    configs.append((1, 64, 2048))
+for B, S, L in configs:
     inp = torch.randint(2, 32768, (B, S), device="cuda")
-    inp[:, 0] = 32768
+    inp[:, 0] = START
 
-    # eager
-    greedy_decode(m, inp, 32768, 32769, max_len=8)  # warm
-    torch.cuda.synchronize(); t0 = time.perf_counter()
-    out_e = greedy_decode(m, inp, 32768, 32769, max_len=L)
-    torch.cuda.synchronize(); te = time.perf_counter() - t0
-    n_e = out_e.shape[1] - 1
+    eager = ""
+    if not args.no_eager:
+        greedy_decode(m, inp, START, END, max_len=8)  # warm
+        out_e, te = timed(lambda: greedy_decode(m, inp, START, END, max_len=L))
+        n_e = out_e.shape[1] - 1
+        eager = f"eager {te*1e3/n_e:.2f} ms/tok ({B*n_e/te:.0f} tok/s) | "
 
-    # graphed
-    dec = GraphedDecoder(m, B=B, S_src=S, max_len=L, start_id=32768,
-                         device=torch.device("cuda"))
-    dec(inp, 32769, max_len=8)  # warm
-    torch.cuda.synchronize(); t0 = time.perf_counter()
-    out_g = dec(inp, 32769, max_len=L)
-    torch.cuda.synchronize(); tg = time.perf_counter() - t0
-
-    # parity up to first EOS per row
-    ok = True
-    for b in range(B):
-        er, gr = out_e[b].tolist(), out_g[b].tolist()
-        for i in range(min(len(er), len(gr))):
-            if er[i] != gr[i]:
-                ok = False
-                break
-            if er[i] == 32769:
-                break
-    print(f"B={B} S={S} L={L}: eager {te*1e3/n_e:.2f} ms/tok "
-          f"({B*n_e/te:.0f} tok/s) | graphed {tg*1e3/L:.3f} ms/tok "
-          f"({B*L/tg:.0f} tok/s) | speedup {te/n_e/(tg/L):.2f}x "
-          f"| parity {'OK' if ok else 'MISMATCH'}")
+    decs = [GraphedDecoder(m, B=B, S_src=S, max_len=L, start_id=START,
+                           device=torch.device("cuda"), fused_attn=f)
+            for f in (False, True)]
+    for d in decs:
+        d(inp, END, max_len=8)  # warm
+    ts, outs = ([], []), [None, None]
+    for _ in range(args.reps):
+        for i, d in enumerate(decs):
+            outs[i], t = timed(lambda: d(inp, END, max_len=L))
+            ts[i].append(t)
+    ok = same_until_end(outs[0], outs[1])
+    if not args.no_eager:
+        ok = ok and same_until_end(out_e, outs[0])
+    tg, tf = statistics.median(ts[0]), statistics.median(ts[1])
+    print(f"B={B} S={S} L={L}: {eager}graphed {stats(ts[0], L)} ms/tok "
+          f"({B*L/tg:.0f} tok/s) | graphed+fused_attn {stats(ts[1], L)} "
+          f"ms/tok ({B*L/tf:.0f} tok/s) | fused/graphed time {tf/tg:.3f} "
+          f"| parity {'OK' if ok else 'MISMATCH'}", flush=True)
 print("decode bench done")

@@ -337,7 +337,8 @@ class DecodeCache:
     """Per-layer packed KV caches + precomputed cross K/V."""
 
     def __init__(self, model: "Transformer", B: int, max_len: int,
-                 enc_output: torch.Tensor, src_pad: torch.Tensor):
+                 enc_output: torch.Tensor, src_pad: torch.Tensor,
+                 fused_attn: bool = False):
         dec = model.decoder
         d = dec.d_model
         layer0 = dec.layers[0]
@@ -355,6 +356,13 @@ class DecodeCache:
         for layer in dec.layers:
             kv = ops.linear(enc_output, layer.mha2.w_kv, layer.mha2.b_kv)
             self.cross_kv.append(kv.view(B, Sk, 2, H, dh))
+        # fused_attn: the decode-attention kernels track the row lengths on
+        # the device and share one workspace across the layers
+        self.kv_len = self.ws = None
+        if fused_attn:
+            self.kv_len = torch.zeros(B, dtype=torch.int32, device=dev)
+            self.ws = ops.decode_attention_workspace(B, H, dh,
+                                                     max(max_len, Sk), dev)
 
 
 @torch.no_grad()
@@ -381,11 +389,15 @@ def decode_step(model, tokens_new, cache: DecodeCache):
         # new row, append k/v in place, attend over positions [0, t].
         qkv = ops.linear(x, layer.mha1.w_qkv, layer.mha1.b_qkv)
         qkv = qkv.view(B, 1, 3, H, dh)
-        cache.self_kv[li][:, t:t + 1] = qkv[:, :, 1:3]
-        q = qkv[:, :, 0].contiguous()
-        kv_hist = cache.self_kv[li][:, :t + 1]
-        k, v = kv_hist.unbind(dim=2)
-        attn1 = ops.fused_attention(q, k, v)  # all cached keys visible
+        if cache.kv_len is not None:
+            attn1 = ops.decode_attention_self(qkv, cache.self_kv[li],
+                                              cache.kv_len, cache.ws)
+        else:
+            cache.self_kv[li][:, t:t + 1] = qkv[:, :, 1:3]
+            q = qkv[:, :, 0].contiguous()
+            kv_hist = cache.self_kv[li][:, :t + 1]
+            k, v = kv_hist.unbind(dim=2)
+            attn1 = ops.fused_attention(q, k, v)  # all cached keys visible
         attn1 = ops.linear(attn1.reshape(B, 1, H * dh),
                            layer.mha1.w_o, layer.mha1.b_o)
         out1 = ops.residual_layernorm(attn1, x, layer.ln1.gamma,
@@ -393,8 +405,12 @@ def decode_step(model, tokens_new, cache: DecodeCache):
         # cross-attention against precomputed encoder K/V
         q2 = ops.linear(out1, layer.mha2.w_q, layer.mha2.b_q)
         q2 = q2.view(B, 1, H, dh)
-        k2, v2 = cache.cross_kv[li].unbind(dim=2)
-        attn2 = ops.fused_attention(q2, k2, v2, kv_pad=cache.src_pad)
+        if cache.kv_len is not None:
+            attn2 = ops.decode_attention_cross(q2, cache.cross_kv[li],
+                                               cache.src_pad, cache.ws)
+        else:
+            k2, v2 = cache.cross_kv[li].unbind(dim=2)
+            attn2 = ops.fused_attention(q2, k2, v2, kv_pad=cache.src_pad)
         attn2 = ops.linear(attn2.reshape(B, 1, H * dh),
                            layer.mha2.w_o, layer.mha2.b_o)
         out2 = ops.residual_layernorm(attn2, out1, layer.ln2.gamma,
@@ -403,17 +419,22 @@ def decode_step(model, tokens_new, cache: DecodeCache):
         x = ops.residual_layernorm(ffn, out2, layer.ln3.gamma,
                                    layer.ln3.beta, layer.ln3.eps)
     cache.pos = t + 1
+    if cache.kv_len is not None:
+        cache.kv_len.add_(1)
     return ops.linear(x, model.w_final, model.b_final)
 
 
 @torch.no_grad()
-def greedy_decode(model, inp, start_id, end_id, max_len=10):
+def greedy_decode(model, inp, start_id, end_id, max_len=10,
+                  fused_attn=False):
     """KV-cached greedy decode.  inp (B, S) int64; returns (B, <=max_len+1)
     token ids starting with start_id; stops early when every sequence has
-    emitted end_id."""
+    emitted end_id.  fused_attn: the single-query decode-attention kernels
+    (ops.decode_attention_self/_cross) in place of the training kernel."""
     B = inp.shape[0]
     enc_output, src_pad = encode(model, inp)
-    cache = DecodeCache(model, B, max_len + 1, enc_output, src_pad)
+    cache = DecodeCache(model, B, max_len + 1, enc_output, src_pad,
+                        fused_attn=fused_attn)
     out = torch.full((B, 1), start_id, dtype=torch.int64, device=inp.device)
     finished = torch.zeros(B, dtype=torch.bool, device=inp.device)
     for _ in range(max_len):
@@ -454,7 +475,11 @@ class GraphedDecoder:
 
     @torch.no_grad()
     def __init__(self, model: "Transformer", B: int, S_src: int, max_len: int,
-                 start_id: int, device):
+                 start_id: int, device, fused_attn: bool = False):
+        """fused_attn: the captured step runs ops.decode_attention_self /
+        _cross (append + attention in one launch each, over an int32 (B,)
+        device length) in place of the pad-mask unmask, the cache
+        index_copy_, the query copy and the training attention kernel."""
         assert max_len >= 4, "warmup+capture advance the position past 3"
         self.model = model
         self.B, self.S_src, self.max_len = B, S_src, max_len
@@ -467,11 +492,21 @@ class GraphedDecoder:
         self.enc_output = torch.zeros(B, S_src, dec.d_model, device=device,
                                       dtype=dt)
         self.src_pad = torch.zeros(B, S_src, dtype=torch.uint8, device=device)
-        self.self_kv = [torch.zeros(B, max_len, 2, H, dh, device=device,
-                                    dtype=dt) for _ in dec.layers]
+        self.fused_attn = fused_attn
+        # fused path: rows past kv_len are never read, so no zero-fill
+        self.self_kv = [(torch.empty if fused_attn else torch.zeros)(
+            B, max_len, 2, H, dh, device=device, dtype=dt)
+            for _ in dec.layers]
         self.cross_kv = [torch.zeros(B, S_src, 2, H, dh, device=device,
                                      dtype=dt) for _ in dec.layers]
-        self.kv_pad = torch.ones(B, max_len, dtype=torch.uint8, device=device)
+        if fused_attn:
+            self.kv_len = torch.zeros(B, dtype=torch.int32, device=device)
+            # allocated here, outside capture; shared by all layers
+            self.ws = ops.decode_attention_workspace(
+                B, H, dh, max(max_len, S_src), device)
+        else:
+            self.kv_pad = torch.ones(B, max_len, dtype=torch.uint8,
+                                     device=device)
         self.tok = torch.zeros(B, max_len + 1, dtype=torch.int64,
                                device=device)
         self.pos = torch.zeros(1, dtype=torch.int64, device=device)
@@ -479,8 +514,9 @@ class GraphedDecoder:
         def step():
             from .. import ops as O
             pos = self.pos
-            # this replay's cache slot becomes visible
-            self.kv_pad.index_fill_(1, pos, 0)
+            if not fused_attn:
+                # this replay's cache slot becomes visible
+                self.kv_pad.index_fill_(1, pos, 0)
             cur = self.tok.index_select(1, pos)            # (B,1)
             pe_row = dec.pe.index_select(0, pos)           # (1,d) model dtype
             # same kernel as the eager decode path -> bit-identical tokens
@@ -488,18 +524,27 @@ class GraphedDecoder:
             for li, layer in enumerate(dec.layers):
                 qkv = O.linear(x, layer.mha1.w_qkv, layer.mha1.b_qkv)
                 qkv = qkv.view(B, 1, 3, H, dh)
-                self.self_kv[li].index_copy_(1, pos, qkv[:, :, 1:3])
-                q = qkv[:, :, 0].contiguous()
-                k, v = self.self_kv[li].unbind(dim=2)
-                attn1 = O.fused_attention(q, k, v, kv_pad=self.kv_pad)
+                if fused_attn:
+                    attn1 = O.decode_attention_self(qkv, self.self_kv[li],
+                                                    self.kv_len, self.ws)
+                else:
+                    self.self_kv[li].index_copy_(1, pos, qkv[:, :, 1:3])
+                    q = qkv[:, :, 0].contiguous()
+                    k, v = self.self_kv[li].unbind(dim=2)
+                    attn1 = O.fused_attention(q, k, v, kv_pad=self.kv_pad)
                 attn1 = O.linear(attn1.reshape(B, 1, H * dh),
                                  layer.mha1.w_o, layer.mha1.b_o)
                 out1 = O.residual_layernorm(attn1, x, layer.ln1.gamma,
                                             layer.ln1.beta, layer.ln1.eps)
                 q2 = O.linear(out1, layer.mha2.w_q, layer.mha2.b_q)
                 q2 = q2.view(B, 1, H, dh)
-                k2, v2 = self.cross_kv[li].unbind(dim=2)
-                attn2 = O.fused_attention(q2, k2, v2, kv_pad=self.src_pad)
+                if fused_attn:
+                    attn2 = O.decode_attention_cross(q2, self.cross_kv[li],
+                                                     self.src_pad, self.ws)
+                else:
+                    k2, v2 = self.cross_kv[li].unbind(dim=2)
+                    attn2 = O.fused_attention(q2, k2, v2,
+                                              kv_pad=self.src_pad)
                 attn2 = O.linear(attn2.reshape(B, 1, H * dh),
                                  layer.mha2.w_o, layer.mha2.b_o)
                 out2 = O.residual_layernorm(attn2, out1, layer.ln2.gamma,
@@ -511,6 +556,8 @@ class GraphedDecoder:
             nxt = O.argmax_lastdim(logits).view(B, 1)
             self.tok.index_copy_(1, pos + 1, nxt)
             self.pos.add_(1)
+            if fused_attn:
+                self.kv_len.add_(1)
 
         # warmup on a side stream, then capture.  capture hint: library
         # GEMM kernels inside the graph (launch cost is replayed away).
@@ -546,8 +593,11 @@ class GraphedDecoder:
             self.cross_kv[li].copy_(
                 kv.view(self.B, self.S_src, 2, layer.mha2.num_heads,
                         layer.mha2.depth))
-        self.kv_pad.fill_(1)
-        self.self_kv and [t.zero_() for t in self.self_kv]
+        if self.fused_attn:
+            self.kv_len.zero_()
+        else:
+            self.kv_pad.fill_(1)
+            self.self_kv and [t.zero_() for t in self.self_kv]
         self.tok.zero_()
         self.tok[:, 0] = self.start_id
         self.pos.zero_()

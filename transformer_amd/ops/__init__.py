@@ -52,6 +52,9 @@ from .functional import (  # noqa: E402
     fused_attention,
     self_attention,
     cross_attention,
+    decode_attention_self,
+    decode_attention_cross,
+    decode_attention_workspace,
     residual_layernorm,
     dropout_residual_layernorm,
     linear_dropout_residual_layernorm,

@@ -73,6 +73,16 @@ std::vector<torch::Tensor> attn_bwd_seg(torch::Tensor q, torch::Tensor k,
                                         torch::Tensor kv_seg, bool causal,
                                         double scale, int64_t mode);
 
+torch::Tensor decode_attn_self(torch::Tensor qkv, torch::Tensor kv_cache,
+                               torch::Tensor kv_len, torch::Tensor ws,
+                               double scale, int64_t nsplit);
+torch::Tensor decode_attn_cross(torch::Tensor q, torch::Tensor kv,
+                                torch::Tensor kv_pad, torch::Tensor ws,
+                                double scale, int64_t nsplit);
+torch::Tensor decode_attn_workspace(int64_t B, int64_t H, int64_t dh,
+                                    int64_t L);
+int64_t decode_attn_nsplit(int64_t BH, int64_t L);
+
 torch::Tensor embed_pe_fwd(torch::Tensor tokens, torch::Tensor weight,
                            torch::Tensor pe,
                            c10::optional<torch::Tensor> positions);
@@ -229,6 +239,28 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("dout"), pybind11::arg("lse"), pybind11::arg("q_seg"),
         pybind11::arg("kv_seg"), pybind11::arg("causal"),
         pybind11::arg("scale"), pybind11::arg("mode") = 0);
+  m.def("decode_attn_self", &decode_attn_self,
+        "single-query self-attention over a (B,Lmax,2,H,dh) cache with "
+        "device-side lengths: appends qkv's K/V row at kv_len[b] (not past "
+        "Lmax) and attends keys [0, kv_len[b]]; kv_len itself is unchanged. "
+        "nsplit 0 = host rule, else forced (tests, sweeps)",
+        pybind11::arg("qkv"), pybind11::arg("kv_cache"),
+        pybind11::arg("kv_len"), pybind11::arg("ws"), pybind11::arg("scale"),
+        pybind11::arg("nsplit") = 0);
+  m.def("decode_attn_cross", &decode_attn_cross,
+        "single-query cross-attention over packed (B,Sk,2,H,dh) K/V; padded "
+        "keys get -1e9 added to the scaled score",
+        pybind11::arg("q"), pybind11::arg("kv"), pybind11::arg("kv_pad"),
+        pybind11::arg("ws"), pybind11::arg("scale"),
+        pybind11::arg("nsplit") = 0);
+  m.def("decode_attn_workspace", &decode_attn_workspace,
+        "zeroed tickets + fp32 partials for key windows up to L; allocate "
+        "once outside graph capture, share per stream only",
+        pybind11::arg("B"), pybind11::arg("H"), pybind11::arg("dh"),
+        pybind11::arg("L"));
+  m.def("decode_attn_nsplit", &decode_attn_nsplit,
+        "the host rule's split count for B*H rows and a key window of L",
+        pybind11::arg("BH"), pybind11::arg("L"));
   m.def("embed_pe_fwd", &embed_pe_fwd, pybind11::arg("tokens"),
         pybind11::arg("weight"), pybind11::arg("pe"),
         pybind11::arg("positions") = pybind11::none());

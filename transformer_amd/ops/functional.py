@@ -396,6 +396,47 @@ def fused_attention(q, k, v, kv_pad=None, causal=False, return_weights=False,
 
 
 # ---------------------------------------------------------------------------
+# Single-query decode attention (forward only, csrc/decode_attn.hip): one
+# launch per attention — split-KV over the grid, K/V append fused, per-row
+# key counts read on the device.
+# ---------------------------------------------------------------------------
+
+def decode_attention_workspace(B, H, dh, L, device=None):
+    """Scratch for decode_attention_self/_cross at these B, H, dh and key
+    windows up to L (pass the larger of the cache length and the source
+    length to serve both).  Allocate it once, outside graph capture; the
+    layers of a step may share it because their calls are stream-ordered,
+    but calls on different streams must not.  CPU: an empty placeholder."""
+    dev = torch.device(device if device is not None else
+                       ("cuda" if torch.cuda.is_available() else "cpu"))
+    if dev.type != "cuda":
+        return torch.zeros(0)
+    with torch.cuda.device(dev):
+        return ext().decode_attn_workspace(B, H, dh, L)
+
+
+def decode_attention_self(qkv, kv_cache, kv_len, ws):
+    """qkv (B,1,3,H,dh), the unsliced packed projection of the new token;
+    kv_cache (B,Lmax,2,H,dh); kv_len (B,) int32 on qkv's device = keys
+    already cached per row.  Stores the new K/V row at kv_cache[b, kv_len[b]]
+    (in place; nothing once a row is full) and attends keys [0, kv_len[b]].
+    The caller advances kv_len (kv_len.add_(1)); the host never reads it."""
+    if qkv.is_cuda:
+        return ext().decode_attn_self(qkv, kv_cache, kv_len, ws,
+                                      1.0 / math.sqrt(qkv.shape[-1]))
+    return R.decode_attention_self(qkv, kv_cache, kv_len)
+
+
+def decode_attention_cross(q, kv, kv_pad, ws):
+    """q (B,1,H,dh), possibly a strided view; kv (B,Sk,2,H,dh); kv_pad
+    (B,Sk) uint8 or None, padded keys under the additive -1e9 rule."""
+    if q.is_cuda:
+        return ext().decode_attn_cross(q, kv, _opt(kv_pad), ws,
+                                       1.0 / math.sqrt(q.shape[-1]))
+    return R.decode_attention_cross(q, kv, kv_pad)
+
+
+# ---------------------------------------------------------------------------
 # Fused (dropout +) residual-add + LayerNorm, eps=1e-6 (K9), alone and as
 # the tail of the sublayer composites: LN(dropout(linear(x)) + res) and the
 # whole FFN block as ONE autograd node each.  The composites' forward runs

@@ -94,6 +94,43 @@ def scaled_dot_product_attention(q, k, v, mask=None, return_weights=False):
 
 
 # ---------------------------------------------------------------------------
+# Single-query decode attention (csrc/decode_attn.hip): one new row per
+# sequence against a (B, Lmax, 2, H, dh) cache with per-row lengths.
+# ---------------------------------------------------------------------------
+
+def decode_attention_self(qkv, kv_cache, kv_len):
+    """qkv (B,1,3,H,dh); kv_cache (B,Lmax,2,H,dh); kv_len (B,) int = valid
+    keys per row BEFORE the call.  Writes qkv's K/V row into
+    kv_cache[b, kv_len[b]] IN PLACE (nothing when kv_len[b] >= Lmax) and
+    attends row b's query over its kv_len[b] cached keys plus the new one.
+    kv_len is left as it is.  Returns (B,1,H,dh)."""
+    B, _, _, H, dh = qkv.shape
+    Lmax = kv_cache.shape[1]
+    out = torch.empty(B, 1, H, dh, dtype=qkv.dtype, device=qkv.device)
+    for b in range(B):
+        n = min(max(int(kv_len[b]), 0), Lmax)
+        if n < Lmax:
+            kv_cache[b, n] = qkv[b, 0, 1:3]
+        kv = torch.cat([kv_cache[b, :n], qkv[b, :, 1:3]], dim=0)  # (n+1,2,H,dh)
+        q = qkv[b, :, 0].permute(1, 0, 2).float()                # (H,1,dh)
+        k, v = (kv[:, s].permute(1, 0, 2).float() for s in (0, 1))
+        out[b] = scaled_dot_product_attention(q, k, v).permute(1, 0, 2)
+    return out
+
+
+def decode_attention_cross(q, kv, kv_pad=None):
+    """q (B,1,H,dh); kv (B,Sk,2,H,dh); kv_pad (B,Sk), non-zero = pad (the
+    additive -1e9 rule).  Returns (B,1,H,dh)."""
+    qt = q.permute(0, 2, 1, 3).float()
+    kt, vt = (kv[:, :, s].permute(0, 2, 1, 3).float() for s in (0, 1))
+    mask = None
+    if kv_pad is not None:
+        mask = (kv_pad != 0).to(torch.float32)[:, None, None, :]
+    out = scaled_dot_product_attention(qt, kt, vt, mask)
+    return out.permute(0, 2, 1, 3).to(q.dtype)
+
+
+# ---------------------------------------------------------------------------
 # K9 — fused residual-add + LayerNorm (post-LN residual, eps=1e-6;
 # reference Encoder.py:13-14,23,27).
 # ---------------------------------------------------------------------------
