@@ -4,7 +4,7 @@ at the model's actual training shapes (GPU box).
     python tools/uni_bench.py [iters]
 
 Per shape, interleaved rounds (guide §5.4 rule 24): report min ms and TF.
-  fwd : gemm_uni_nt (counted-vmcnt + setprio)  vs  gemm_nt (r1 dispatch)
+  fwd : gemm_uni_nt                            vs  gemm_nt (r1 dispatch)
         vs hipBLASLt fused epilogue (F.linear/_addmm_activation)
   dX  : gemm_uni_nn (NTxTR)                    vs  torch.matmul (r1)
   dW  : gemm_uni_tn (TRxTR, splitr sweep)      vs  gemm_dw / torch.matmul
@@ -77,40 +77,11 @@ DW = [
 ]
 
 
-SCHED_NAMES = {0: "cnt+prio", 1: "cnt", 2: "r1-style", 3: "cnt+stat",
-               4: "cnt+Bq1", 5: "ring", 6: "nobar", 7: "2bar", 8: "ring128x2"}
-
-
-def sched_ab(iters):
-    print("== NT schedule A/B (gemm_uni_nt_ab) ==")
-    dt = torch.bfloat16
-    for M, N, K, _, tag in [FWD[0], FWD[3], FWD[4], FWD[6]]:
-        a = torch.randn(M, K, device="cuda", dtype=dt)
-        w = torch.randn(N, K, device="cuda", dtype=dt) * 0.05
-        scheds = [2, 5, 6, 8]
-        fns = [lambda s=s: E.gemm_uni_nt_ab(a, w, s) for s in scheds]
-        fns.append(lambda: E.gemm_nt(a, w, torch.Tensor(), 0))
-        r = bench_pair(fns, iters)
-        parts = " | ".join(f"{SCHED_NAMES[s]} {tf(M,N,K,r[i]):5.0f}TF"
-                           for i, s in enumerate(scheds))
-        print(f"{tag:18s} {parts} | r1-nt {tf(M,N,K,r[-1]):5.0f}TF")
-        # numerics sanity on one round
-        ref = (a.float() @ w.float().T)
-        for s in scheds:
-            c = E.gemm_uni_nt_ab(a, w, s).float()
-            err = (c - ref).abs().max() / ref.abs().max().clamp(min=1)
-            assert err < 0.03, (tag, s, err)
-
-
 def main():
     iters = int(sys.argv[1]) if len(sys.argv) > 1 else 30
     dev = "cuda"
     dt = torch.bfloat16
     torch.manual_seed(0)
-
-    if len(sys.argv) > 2 and sys.argv[2] == "sched":
-        sched_ab(iters)
-        return
 
     print("== forward: uni vs r1 gemm_nt vs hipBLASLt ==")
     for M, N, K, epi, tag in FWD:
@@ -145,7 +116,7 @@ def main():
     for Mt, N, K, tag in DW:
         dy = torch.randn(Mt, N, device=dev, dtype=dt) * 0.05
         x = torch.randn(Mt, K, device=dev, dtype=dt) * 0.05
-        fns = [lambda: E.gemm_dw(dy, x, None, None, None),
+        fns = [lambda: E.gemm_dw(dy, x),
                lambda: torch.matmul(dy.t(), x)]
         splits = [1, 2, 4, 8, 16, 32]
         for s in splits:

@@ -1166,13 +1166,8 @@ static std::vector<torch::Tensor> attn_bwd_impl(
   const long do_rs = (long)H * DH;
   // QT=64 at long sequence halves the per-tile staging/sync fixed costs
   // (the S=4096 backward's dominant overhead); QT=32 keeps short-seq
-  // tail efficiency.  TFMX_ATTN_QT forces either for A/B.
-  static const int qt_force = [] {
-    const char* e = getenv("TFMX_ATTN_QT");
-    return e ? atoi(e) : 0;
-  }();
-  const bool qt64 = qt_force ? (qt_force == 64)
-                             : (Sq >= 1024 && Sk >= 1024);
+  // tail efficiency.
+  const bool qt64 = Sq >= 1024 && Sk >= 1024;
   if (q_seg.defined()) {
     TORCH_CHECK(!causal || Sq == Sk, "causal segments require Sq == Sk");
     torch::Tensor rng;

@@ -16,8 +16,7 @@ torch::Tensor gemm128_nt(torch::Tensor a, torch::Tensor w, torch::Tensor bias,
                          int64_t epilogue, c10::optional<torch::Tensor> out);
 torch::Tensor gemm_dw(torch::Tensor dy, torch::Tensor x,
                       c10::optional<torch::Tensor> out,
-                      c10::optional<torch::Tensor> db,
-                      c10::optional<torch::Tensor> cw_cached);
+                      c10::optional<torch::Tensor> db);
 torch::Tensor gemm_nn(torch::Tensor a, torch::Tensor b,
                       c10::optional<torch::Tensor> out);
 torch::Tensor gemm_tn(torch::Tensor a, torch::Tensor b,
@@ -34,8 +33,6 @@ torch::Tensor gemm_uni_nn(torch::Tensor a, torch::Tensor w,
 torch::Tensor gemm_uni_tn(torch::Tensor dy, torch::Tensor x,
                           c10::optional<torch::Tensor> out, int64_t splitr);
 bool gemm_uni_viable(int M, int N, int K);
-torch::Tensor gemm_uni_nt_ab(torch::Tensor a, torch::Tensor w,
-                             int64_t sched);
 torch::Tensor relu_bwd(torch::Tensor dy, torch::Tensor y);
 std::vector<torch::Tensor> relu_bwd_db(torch::Tensor dy, torch::Tensor y,
                                        c10::optional<torch::Tensor> db_out);
@@ -157,8 +154,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "optional fused bias grad db[N]",
         pybind11::arg("dy"), pybind11::arg("x"),
         pybind11::arg("out") = pybind11::none(),
-        pybind11::arg("db") = pybind11::none(),
-        pybind11::arg("cw") = pybind11::none());
+        pybind11::arg("db") = pybind11::none());
   m.def("gemm128_nt", &gemm128_nt, "128x128 NT path, no 256 dispatch (A/B)",
         pybind11::arg("a"), pybind11::arg("w"), pybind11::arg("bias"),
         pybind11::arg("epilogue"), pybind11::arg("out") = pybind11::none());
@@ -197,8 +193,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("dy"), pybind11::arg("x"),
         pybind11::arg("out") = c10::nullopt, pybind11::arg("splitr") = 1);
   m.def("gemm_uni_viable", &gemm_uni_viable);
-  m.def("gemm_uni_nt_ab", &gemm_uni_nt_ab,
-        "schedule A/B variants of the uni NT kernel (bench only)");
   m.def("colsum", &colsum,
         "column sums of a row-strided bf16 matrix; row-streaming kernel on "
         "16-byte-aligned inputs, TFMX_COLSUM=cols keeps the column kernel",

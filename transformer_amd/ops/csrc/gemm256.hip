@@ -213,8 +213,7 @@ DEV_INLINE int epi_chunk8(int row, int c) {
 // BM_/BN_ in {256, 128}: per-wave output (BM_/2) x (BN_/4); narrower
 // instances keep the chip full on small-M/N shapes with the same
 // pipelined phase structure.
-template <int EPILOGUE, int BM_, int BN_, int STORE, int ORDER = 0,
-          int XCDMAP = 1>
+template <int EPILOGUE, int BM_, int BN_, int STORE>
 __global__ __launch_bounds__(G_THREADS, 1)
 void gemm256_kernel(const short* __restrict__ A, const short* __restrict__ B,
                     const short* __restrict__ bias, short* __restrict__ C,
@@ -229,18 +228,16 @@ void gemm256_kernel(const short* __restrict__ A, const short* __restrict__ B,
   extern __shared__ short smem[];
   const int lane = threadIdx.x & 63;
 
-  // XCD-aware bijective workgroup remap (8 XCDs, private L2s) + tile
-  // walk order (ORDER 0: m-major — consecutive wgs share the A panel;
-  // 1: n-major — share the B panel.  At L3-resident huge-N shapes the
-  // walk order decides which operand streams from HBM).
+  // XCD-aware bijective workgroup remap (8 XCDs, private L2s), then an
+  // m-major tile walk: consecutive wgs share the A panel.
   int nwg = nbm * nbn;
   int wg = blockIdx.x;
-  if (XCDMAP) {
+  {
     int q = nwg / 8, r = nwg % 8, x = wg % 8, o = wg / 8;
     wg = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + o;
   }
-  const int bm0 = (ORDER ? (wg % nbm) : (wg / nbn)) * BM_;
-  const int bn0 = (ORDER ? (wg / nbm) : (wg % nbn)) * BN_;
+  const int bm0 = (wg / nbn) * BM_;
+  const int bn0 = (wg % nbn) * BN_;
 
   const int wid = threadIdx.x >> 6;
   const int wm = (wid >> 2) * (BM_ / 2);  // wave rows
@@ -565,35 +562,20 @@ torch::Tensor gemm256_nt(torch::Tensor a, torch::Tensor w, torch::Tensor bias,
   else if (N % 2 == 0 && aligned(c.data_ptr(), 4) && aligned(auxp, 4))
     vec = 2;
   if (store == -2) store = vec == 8 ? 2 : 0;
-  // tile-walk order / XCD-remap variants (TFMX_G256_ORDER=nm,
-  // TFMX_G256_XCD=0 for the A/B prober; huge-N shapes pick n-major by
-  // the measured rule below)
-  static const int env_order = [] {
-    const char* e = getenv("TFMX_G256_ORDER");
-    return e ? (e[0] == 'n' ? 1 : 0) : -1;
-  }();
-  static const int env_xcd = [] {
-    const char* e = getenv("TFMX_G256_XCD");
-    return e ? atoi(e) : -1;
-  }();
-  const int order = env_order >= 0 ? env_order : 0;
-  const int xcd = env_xcd >= 0 ? env_xcd : 1;
   auto launch = [&](auto epi, auto bmc, auto bnc) {
     constexpr int E = decltype(epi)::value;
     constexpr int BM_ = decltype(bmc)::value;
     constexpr int BN_ = decltype(bnc)::value;
-    auto go = [&](auto sc, auto oc, auto xc) {
+    auto go = [&](auto sc) {
       constexpr int SV = decltype(sc)::value;
-      constexpr int OV = decltype(oc)::value;
-      constexpr int XV = decltype(xc)::value;
       static bool attr_set = false;  // one per kernel instance
       if (!attr_set) {
         (void)hipFuncSetAttribute(
-            (const void*)gemm256_kernel<E, BM_, BN_, SV, OV, XV>,
+            (const void*)gemm256_kernel<E, BM_, BN_, SV>,
             hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         attr_set = true;
       }
-      gemm256_kernel<E, BM_, BN_, SV, OV, XV>
+      gemm256_kernel<E, BM_, BN_, SV>
           <<<nbm * nbn, G_THREADS, smem, stream>>>(
               (const short*)a.data_ptr(), (const short*)w.data_ptr(),
               (const short*)biasp, (short*)c.data_ptr(), M, N, K, K, K,
@@ -602,17 +584,9 @@ torch::Tensor gemm256_nt(torch::Tensor a, torch::Tensor w, torch::Tensor bias,
     using I0 = std::integral_constant<int, 0>;
     using I1 = std::integral_constant<int, 1>;
     using I2 = std::integral_constant<int, 2>;
-    // The tile-walk / XCD prober variants exist on the lds arm only (it
-    // takes the narrow paths itself where the wide stores do not apply).
-    if (order || !xcd) {
-      TORCH_CHECK(!epi_env || store == 2,
-                  "TFMX_G256_ORDER/XCD probes run on the lds epilogue");
-      if (order) { if (xcd) go(I2{}, I1{}, I1{}); else go(I2{}, I1{}, I0{}); }
-      else go(I2{}, I0{}, I0{});
-    }
-    else if (store == 0) go(I0{}, I0{}, I1{});
-    else if (store == 1) go(I1{}, I0{}, I1{});
-    else go(I2{}, I0{}, I1{});
+    if (store == 0) go(I0{});
+    else if (store == 1) go(I1{});
+    else go(I2{});
   };
   using E0 = std::integral_constant<int, 0>;
   using E1 = std::integral_constant<int, 1>;

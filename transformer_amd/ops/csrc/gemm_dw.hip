@@ -41,11 +41,10 @@ namespace {
 // Within a subtile the m-row is stored permuted (pr = low-3-bits<<2 | top-2)
 // so the four 16-lane tr-read groups (m windows 8 apart) interleave across
 // the 512-B subtile instead of stacking on the same 256-B bank row.
-template <int ROWS = 64>
 DEV_INLINE int dw_img(int m, int col) {
   const int r = m & 31;
   const int pr = ((r & 7) << 2) | (r >> 3);
-  return ((col >> 4) * (ROWS / 32) + (m >> 5)) * 512 + pr * 16 + (col & 15);
+  return ((col >> 4) * (DW_BM / 32) + (m >> 5)) * 512 + pr * 16 + (col & 15);
 }
 
 // Stage a [64 m][128 col] block from global (row-major, ldg elems/row) into
@@ -53,15 +52,14 @@ DEV_INLINE int dw_img(int m, int col) {
 // along col) + 4 ds_writes.  Out-of-range token rows and columns are
 // ZERO-filled — rows are contraction terms here, so clamping (as the NT
 // kernels do for discarded output rows) would add duplicate contributions.
-template <int COLS = 128, int ROWS = 64>
 DEV_INLINE void dw_stage(const short* __restrict__ g, long ldg, long m0,
                          long mmax, int col0, int ncols, short* lds) {
   const int t = threadIdx.x;
 #pragma unroll
-  for (int p = 0; p < ROWS * COLS / 2048; ++p) {
-    int idx = p * DW_THREADS + t;      // ROWS*COLS/8 chunks of 8 shorts
-    int m = idx / (COLS / 8);
-    int c8 = (idx % (COLS / 8)) << 3;
+  for (int p = 0; p < DW_BM * 128 / 2048; ++p) {
+    int idx = p * DW_THREADS + t;      // 64*128/8 chunks of 8 shorts
+    int m = idx / (128 / 8);
+    int c8 = (idx % (128 / 8)) << 3;
     long gm = m0 + m;
     s16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
     if (gm < mmax) {
@@ -74,28 +72,26 @@ DEV_INLINE void dw_stage(const short* __restrict__ g, long ldg, long m0,
       }
     }
     // image dest: subtile row-half [m][c8..c8+8) — contiguous 16 B
-    *(s16x4*)&lds[dw_img<ROWS>(m, c8)] = {v[0], v[1], v[2], v[3]};
-    *(s16x4*)&lds[dw_img<ROWS>(m, c8 + 4)] = {v[4], v[5], v[6], v[7]};
+    *(s16x4*)&lds[dw_img(m, c8)] = {v[0], v[1], v[2], v[3]};
+    *(s16x4*)&lds[dw_img(m, c8 + 4)] = {v[4], v[5], v[6], v[7]};
   }
 }
 
 // Transpose-read one 4-deep fragment slice: returns T[mb..mb+4)[colb + n]
 // for this lane's n-role (n = lane & 15).  mb must be a multiple of 4
 // within one 32-m subtile.
-template <int ROWS = 64>
 DEV_INLINE s16x4d dw_tr4(const short* lds, int mb, int colb) {
   const int mp = threadIdx.x & 15;   // this lane's address role
-  const int off = dw_img<ROWS>(mb + (mp >> 2), colb + 4 * (mp & 3));
+  const int off = dw_img(mb + (mp >> 2), colb + 4 * (mp & 3));
   return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
       (__attribute__((address_space(3))) s16x4d*)(
           const_cast<short*>(&lds[off])));
 }
 
 // Full 8-deep bf16x8 fragment: contraction ms..ms+8, column colb + (l&15).
-template <int ROWS = 64>
 DEV_INLINE bf16x8d dw_frag(const short* lds, int ms, int colb) {
-  s16x4d lo = dw_tr4<ROWS>(lds, ms, colb);
-  s16x4d hi = dw_tr4<ROWS>(lds, ms + 4, colb);
+  s16x4d lo = dw_tr4(lds, ms, colb);
+  s16x4d hi = dw_tr4(lds, ms + 4, colb);
   s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
   return (bf16x8d)v;
 }
@@ -105,12 +101,11 @@ DEV_INLINE bf16x8d dw_frag(const short* lds, int ms, int colb) {
 // inverse row permutation is applied to the per-lane SOURCE address — no
 // register bounce, no ds_write pass (guide §5 rule 1).  Each wave stages 4
 // of the 16 1-KiB chunks.
-template <int COLS = 128, int ROWS = 64>
 DEV_INLINE void dw_stage_glds(const short* __restrict__ g, long ldg, long m0,
                               int col0, short* lds) {
   const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
-  for (int p = 0; p < ROWS * COLS / 2048; ++p) {
+  for (int p = 0; p < DW_BM * 128 / 2048; ++p) {
     const int chunk = p * 4 + wid;
     const int d = chunk * 1024 + lane * 16;  // dest byte in image
     const int e = d >> 1;                    // dest element
@@ -118,8 +113,8 @@ DEV_INLINE void dw_stage_glds(const short* __restrict__ g, long ldg, long m0,
     const int we = e & 511;
     const int pr = we >> 4;
     const int r = ((pr & 3) << 3) | (pr >> 2);     // inverse permutation
-    const int m = (sub % (ROWS / 32)) * 32 + r;
-    const int col = (sub / (ROWS / 32)) * 16 + (we & 15);
+    const int m = (sub % (DW_BM / 32)) * 32 + r;
+    const int col = (sub / (DW_BM / 32)) * 16 + (we & 15);
     __builtin_amdgcn_global_load_lds(
         (const __attribute__((address_space(1))) void*)(g + (m0 + m) * ldg +
                                                         col0 + col),
@@ -135,30 +130,21 @@ DEV_INLINE void dw_stage_glds(const short* __restrict__ g, long ldg, long m0,
 // second launch_bounds arg pins >=4 waves/SIMD (VGPR cap 128): the DB
 // variant otherwise allocates 134 VGPRs and drops a whole workgroup of
 // block-level overlap per CU (measured -20% end-to-end).
-typedef __bf16 bf16x4d __attribute__((ext_vector_type(4)));
-
-// X16: use v_mfma_f32_16x16x16_bf16 (4-deep, 2-VGPR operands) so each
-// ds_read_b64_tr_b16 result feeds an MFMA DIRECTLY — the 16x16x32 path
-// pays ~65 v_mov per 64-m block pairing two v4i16 tr-reads into each
-// 4-VGPR operand (seen in the compiled loop; ~24% of the MFMA issue
-// time).  Same LDS traffic, twice the (half-size) MFMA instructions.
-template <bool SPLIT, bool DB, bool NOBAR = true, bool X16 = false,
-          int BM = DW_BM, int RING = 2>
+template <bool SPLIT, bool DB>
 __global__ __launch_bounds__(DW_THREADS)
 void gemm_dw_kernel(const short* __restrict__ dY, const short* __restrict__ X,
                     short* __restrict__ C, float* __restrict__ CW,
                     float* __restrict__ DBW, int M,
                     int N, int K, long m_per_slice, int nbk) {
-  // RING-slot staging ring (PMC: this kernel fetches each operand from
-  // HBM once — L2 absorbs all tile re-reads — so it is pipeline-stall
-  // bound, not traffic bound).  RING=2: prefetch block t+1, drain fully
-  // at the boundary — but a 64-token block is only ~550 MFMA cycles,
-  // under the ~900-cycle HBM latency, so the boundary drain stalls
-  // (SQ_WAIT_ANY ~50%, profiles/r02_pmc_summary.md).  RING=3 stages
-  // t+2 as well and waits the boundary with a COUNTED vmcnt (t+2's
-  // loads ride across), trading LDS 64->96 KiB (2 -> 1 block/CU).
-  __shared__ short a_img[RING][BM * DW_BN];  // dY block
-  __shared__ short b_img[RING][BM * DW_BK];  // X block
+  // Two staging slots: prefetch block t+1, drain fully at the boundary.
+  // (PMC: this kernel fetches each operand from HBM once — L2 absorbs all
+  // tile re-reads — so it is pipeline-stall bound, not traffic bound; a
+  // 64-token block is only ~550 MFMA cycles, under the ~900-cycle HBM
+  // latency, so the boundary drain stalls: SQ_WAIT_ANY ~50%,
+  // profiles/r02_pmc_summary.md.  A 3-slot ring with a counted vmcnt cost
+  // a block/CU of occupancy and measured slower — docs/PERF.md.)
+  __shared__ short a_img[2][DW_BM * DW_BN];  // dY block
+  __shared__ short b_img[2][DW_BM * DW_BK];  // X block
 
   // XCD-aware bijective remap: consecutive logical tiles (same n-block,
   // varying k) land on the SAME XCD, so a dY slice is read into one XCD's
@@ -201,33 +187,25 @@ void gemm_dw_kernel(const short* __restrict__ dY, const short* __restrict__ X,
   // staging helper: block starting at token row `mb` into slot `sl`
   auto stage_blk = [&](long mb, int sl) {
     if (mb >= m_hi) return;
-    if (mb + BM <= m_hi && a_full)
-      dw_stage_glds<128, BM>(dY, N, mb, bn0, a_img[sl]);
+    if (mb + DW_BM <= m_hi && a_full)
+      dw_stage_glds(dY, N, mb, bn0, a_img[sl]);
     else
-      dw_stage<128, BM>(dY, N, mb, m_hi, bn0, N, a_img[sl]);
-    if (mb + BM <= m_hi && b_full)
-      dw_stage_glds<128, BM>(X, K, mb, bk0, b_img[sl]);
+      dw_stage(dY, N, mb, m_hi, bn0, N, a_img[sl]);
+    if (mb + DW_BM <= m_hi && b_full)
+      dw_stage_glds(X, K, mb, bk0, b_img[sl]);
     else
-      dw_stage<128, BM>(X, K, mb, m_hi, bk0, K, b_img[sl]);
+      dw_stage(X, K, mb, m_hi, bk0, K, b_img[sl]);
   };
 
-  // Prologue: stage block 0 (and, at RING=3, block 1), drain block 0.
-  // The counted wait (vmcnt(8): block 1's 8 glds stay in flight) is only
-  // valid when block 1 was glds-staged (full rows + full cols) — the
-  // guarded register path issues no glds to count.
+  // Prologue: stage block 0 and drain it.
   stage_blk(m_lo, 0);
-  if (RING == 3) stage_blk(m_lo + BM, 1 % RING);
-  if (RING == 3 && a_full && b_full && m_lo + 2 * BM <= m_hi) {
-    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-  } else {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
-  for (long m0 = m_lo; m0 < m_hi; m0 += BM) {
+  for (long m0 = m_lo; m0 < m_hi; m0 += DW_BM) {
     if (do_db) {
 #pragma unroll
-      for (int p = 0; p < BM / 8; ++p) {
+      for (int p = 0; p < DW_BM / 8; ++p) {
         const long gm = m0 + p * 8 + (threadIdx.x >> 5);
         if (gm < m_hi && bn0 + db_c4 + 4 <= N) {
           s16x4 v = *(const s16x4*)(dY + gm * N + bn0 + db_c4);
@@ -241,81 +219,40 @@ void gemm_dw_kernel(const short* __restrict__ dY, const short* __restrict__ X,
         }
       }
     }
-    const int cur = (int)((m0 - m_lo) / BM);
-    const short* a_lds = a_img[cur % RING];
-    const short* b_lds = b_img[cur % RING];
+    const int cur = (int)((m0 - m_lo) / DW_BM);
+    const short* a_lds = a_img[cur % 2];
+    const short* b_lds = b_img[cur % 2];
     // Prologue staged block 0; here prefetch block cur+1 into the other
     // slot (its previous tenant was consumed last block) — all glds
     // issued in phase 0, the rest of the block to land before the
     // boundary vmcnt(0) (template schedule, see gemm256.hip).
-    const long mN = m0 + BM;
+    const long mN = m0 + DW_BM;
     const bool pf = mN < m_hi;
     bf16x8d af[4], bf_[4];
-    s16x4d al[4], ah[4], bl[4], bh[4];
 #pragma unroll
-    for (int ph = 0; ph < BM / 32; ++ph) {
+    for (int ph = 0; ph < DW_BM / 32; ++ph) {
       const int ko = ph * 32 + kg * 8;
-      if (!NOBAR && ph) __builtin_amdgcn_s_barrier();
-      if (X16) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          al[i] = dw_tr4<BM>(a_lds, ko, wn + i * 16);
-          ah[i] = dw_tr4<BM>(a_lds, ko + 4, wn + i * 16);
-        }
+      for (int i = 0; i < 4; ++i) af[i] = dw_frag(a_lds, ko, wn + i * 16);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          bl[j] = dw_tr4<BM>(b_lds, ko, wk + j * 16);
-          bh[j] = dw_tr4<BM>(b_lds, ko + 4, wk + j * 16);
-        }
-      } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          af[i] = dw_frag<BM>(a_lds, ko, wn + i * 16);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          bf_[j] = dw_frag<BM>(b_lds, ko, wk + j * 16);
-      }
-      if (ph == 0 && pf) {
-        // stage the NEXT un-staged block: t+1 at RING=2, t+2 at RING=3
-        const long mS = (RING == 3) ? mN + BM : mN;
-        if (mS < m_hi) stage_blk(mS, (int)((cur + RING - 1) % RING));
-      }
-      // NOBAR: no intra-block barriers — all phases read the SAME LDS
-      // slot (synced at the block boundary), fragments are wave-private
+      for (int j = 0; j < 4; ++j) bf_[j] = dw_frag(b_lds, ko, wk + j * 16);
+      if (ph == 0 && pf) stage_blk(mN, (cur + 1) % 2);
+      // No intra-block barriers — all phases read the SAME LDS slot
+      // (synced at the block boundary), fragments are wave-private
       // registers and the glds prefetch lands in the OTHER slot under
       // vmcnt; the compiler tracks the LDS-read -> MFMA dependencies and
       // software-pipelines the next phase's reads under this phase's
-      // MFMA burst.  else: full s_barrier + lgkmcnt(0) drains per phase
-      // keep the 4 waves in lockstep (A/B via TFMX_DW_BAR=1).
-      if (!NOBAR) {
-        __builtin_amdgcn_s_barrier();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      }
+      // MFMA burst.
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if (X16) {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(
-                (bf16x4d)al[i], (bf16x4d)bl[j], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(
-                (bf16x4d)ah[i], (bf16x4d)bh[j], acc[i][j], 0, 0, 0);
-          } else {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                af[i], bf_[j], acc[i][j], 0, 0, 0);
-          }
-        }
+        for (int j = 0; j < 4; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              af[i], bf_[j], acc[i][j], 0, 0, 0);
     }
-    // boundary: block t+1's stages must have landed.  RING=3 leaves
-    // block t+2's 8 glds in flight across the barrier (vmcnt(8)) — valid
-    // only when t+2 really was glds-staged (m0+3*BM fits and the tile is
-    // full); otherwise drain (the guarded path's loads are
-    // compiler-waited before its ds_writes, as at RING=2).
-    if (RING == 3 && a_full && b_full && m0 + 3 * BM <= m_hi) {
-      asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+    // boundary: block t+1's stages must have landed (the guarded path's
+    // loads are compiler-waited before its ds_writes).
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
   }
 
@@ -378,8 +315,7 @@ __global__ void dw_cast_kernel(const float* __restrict__ cw,
 // same pass (no separate colsum read of dY).
 torch::Tensor gemm_dw(torch::Tensor dy, torch::Tensor x,
                       c10::optional<torch::Tensor> out,
-                      c10::optional<torch::Tensor> db,
-                      c10::optional<torch::Tensor> cw_cached) {
+                      c10::optional<torch::Tensor> db) {
   TORCH_CHECK(dy.is_cuda() && dy.dtype() == torch::kBFloat16 &&
               dy.dim() == 2 && dy.is_contiguous(), "gemm_dw: bad dy");
   TORCH_CHECK(x.is_cuda() && x.dtype() == torch::kBFloat16 && x.dim() == 2 &&
@@ -396,29 +332,19 @@ torch::Tensor gemm_dw(torch::Tensor dy, torch::Tensor x,
   } else {
     c = torch::empty({N, K}, dy.options());
   }
-  // Tile-size choice: the 256x256 8-wave kernel halves dY/X re-reads but
-  // MEASURED SLOWER at every model shape (tools/gemm_bench.py: QKV dW
-  // 0.155 vs 0.081 ms, FFN1 0.149 vs 0.076) — the extra split-M slices'
-  // fp32 atomic traffic and the 8-wave barrier cost exceed the re-read
-  // savings, so the 128-tile kernel is the only dispatch target.
+  // A 256x256 8-wave tile halved dY/X re-reads but measured slower at
+  // every model shape (QKV dW 0.155 vs 0.081 ms, FFN1 0.149 vs 0.076), so
+  // this 128-tile kernel is the only one.
   const int nbn = cdiv(N, DW_BN), nbk = cdiv(K, DW_BK);
   const int ntiles = nbn * nbk;
-  // slices: fill >=DW_TARGET_WGS workgroups, 64-token quanta.  More slices
+  // slices: fill >=target_wgs workgroups, 64-token quanta.  More slices
   // = more parallelism but more fp32 atomic traffic + per-WG prologue;
-  // 512 measured best (sweepable via TFMX_DW_WGS for tools/gemm_bench.py).
-  static int target_wgs = [] {
-    const char* e = getenv("TFMX_DW_WGS");
-    return e ? atoi(e) : 512;
-  }();
-  static const bool use_bm32 = [] {
-    const char* e = getenv("TFMX_DW_BM");
-    return e && atoi(e) == 32;
-  }();
-  const int bm = use_bm32 ? 32 : DW_BM;
-  int nslices = (int)min((M + bm - 1) / bm,
+  // 512 measured best.
+  constexpr int target_wgs = 512;
+  int nslices = (int)min((M + DW_BM - 1) / DW_BM,
                          (long)cdiv(target_wgs, ntiles));
   long m_per_slice = (M + nslices - 1) / nslices;
-  m_per_slice = (m_per_slice + bm - 1) / bm * bm;
+  m_per_slice = (m_per_slice + DW_BM - 1) / DW_BM * DW_BM;
   nslices = (int)((M + m_per_slice - 1) / m_per_slice);
   dim3 grid(ntiles, nslices);
   auto stream = at::hip::getCurrentHIPStream();
@@ -431,33 +357,11 @@ torch::Tensor gemm_dw(torch::Tensor dy, torch::Tensor x,
     dbw = torch::zeros({N}, dy.options().dtype(torch::kFloat32));
     dbw_p = dbw.data_ptr<float>();
   }
-  static const bool use_bar = [] {
-    const char* e = getenv("TFMX_DW_BAR");
-    return e && atoi(e) != 0;
-  }();
-  static const bool ring3 = [] {
-    const char* e = getenv("TFMX_DW_RING");
-    return e && atoi(e) == 3;
-  }();
-  static const bool use_x16 = [] {
-    const char* e = getenv("TFMX_DW_X16");
-    return e && atoi(e) != 0;
-  }();
   auto launch = [&](auto split, auto dbc, float* cwp) {
     constexpr bool SP = decltype(split)::value, DBV = decltype(dbc)::value;
-    auto kfn = use_bm32
-        ? gemm_dw_kernel<SP, DBV, true, false, 32>
-        : (ring3
-               ? gemm_dw_kernel<SP, DBV, true, false, DW_BM, 3>
-               : (use_x16
-                      ? (use_bar ? gemm_dw_kernel<SP, DBV, false, true>
-                                 : gemm_dw_kernel<SP, DBV, true, true>)
-                      : (use_bar ? gemm_dw_kernel<SP, DBV, false, false>
-                                 : gemm_dw_kernel<SP, DBV, true, false>)));
-    kfn<<<grid, DW_THREADS, 0, stream>>>(
-            (const short*)dy.data_ptr(), (const short*)x.data_ptr(),
-            (short*)c.data_ptr(), cwp, dbw_p, (int)M, N, K, m_per_slice,
-            nbk);
+    gemm_dw_kernel<SP, DBV><<<grid, DW_THREADS, 0, stream>>>(
+        (const short*)dy.data_ptr(), (const short*)x.data_ptr(),
+        (short*)c.data_ptr(), cwp, dbw_p, (int)M, N, K, m_per_slice, nbk);
   };
   using T = std::true_type;
   using F = std::false_type;
@@ -466,19 +370,10 @@ torch::Tensor gemm_dw(torch::Tensor dy, torch::Tensor x,
   } else {
     // Disjoint per-slice fp32 partials, plain stores, no zeroing needed
     // (every element of every slice is written); reduced by a
-    // chip-filling pass.  `cw_cached` (an optional caller workspace from
-    // the old atomic scheme) is reused as backing storage when large
-    // enough.
+    // chip-filling pass.
     long nk = (long)N * K;
-    torch::Tensor cw;
-    if (cw_cached.has_value() &&
-        cw_cached->numel() >= (long)nslices * nk &&
-        cw_cached->dtype() == torch::kFloat32) {
-      cw = *cw_cached;
-    } else {
-      cw = torch::empty({(long)nslices * nk},
-                        dy.options().dtype(torch::kFloat32));
-    }
+    torch::Tensor cw = torch::empty({(long)nslices * nk},
+                                    dy.options().dtype(torch::kFloat32));
     if (has_db) launch(T{}, T{}, cw.data_ptr<float>());
     else launch(T{}, F{}, cw.data_ptr<float>());
     dw_reduce_kernel<<<(nk + 255) / 256, 256, 0, stream>>>(

@@ -15,15 +15,12 @@
 // (reference contract rows K1/K7/K8/K12: Attention.py:46-50, point_ffn.py:
 // 5-6, Transformer.py:16 — their backward GEMMs.)
 //
-// Schedule: 4 quadrant phases per K-tile (BK=64), glds prefetch of tile
-// t+1 issued in the first two phases, one vmcnt(0) per K-tile at the
-// boundary (the gemm256.hip schedule).  A full counted-vmcnt /
-// consumption-ordered variant and per-quad / static s_setprio forms were
-// built and MEASURED SLOWER on MI355X at every model shape
-// (profiles/r2 sched A/B: counted 557-930 TF vs drain 600-1003; setprio
-// -2..-4% — T5 is null-to-negative on this lockstep phase structure, and
-// the per-tile drain already gives loads >=2.5 phases to land); they are
-// kept as SCHED template variants for the bench tool only.
+// Schedule: 4 quadrant phases per K-tile (BK=64); the whole glds prefetch
+// of tile t+1 is issued in the first phase, no barrier separates the
+// phases, and one vmcnt(0) + barrier per K-tile closes the boundary.
+// docs/PERF.md ("The schedule A/B that settled the GEMM question" and its
+// final addendum) records the counted-vmcnt, s_setprio, lockstep-barrier
+// and single-slot ring schedules this one was measured against.
 //
 // Constraints (dispatched shapes all qualify; host falls back otherwise):
 // K % 64 == 0, and TR-mode operands must be allocated out to the tile
@@ -139,7 +136,7 @@ DEV_INLINE bf16x8u u_frag_tr(const short* lds, int ms, int colb) {
 
 #define U_BARRIER() __builtin_amdgcn_s_barrier()
 #define U_WAIT_LGKM0() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-#define U_WAIT_VM(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
+#define U_WAIT_VM0() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
 
 // ---------------------------------------------------------------------------
 // The kernel.  BM_ = 256 always (the 128 instance lives in gemm.hip);
@@ -147,15 +144,7 @@ DEV_INLINE bf16x8u u_frag_tr(const short* lds, int ms, int colb) {
 // 1 ReLU.  SPLITR: >0 = red axis sliced across blockIdx.y, fp32 partials.
 // ---------------------------------------------------------------------------
 
-// SCHED variants (A/B; tools/uni_bench.py — the default is the measured
-// winner):
-//   0 counted waits + per-quad s_setprio
-//   1 counted waits, no setprio
-//   2 r1-style: all A staged q0, B q1, vmcnt(0) at end-q3, no setprio
-//   3 counted waits + static young-half priority (T5 static form)
-//   4 counted waits, no setprio, B issued at q1 (balanced bursts)
-template <int EPILOGUE, int BN_, bool TRA, bool TRB, bool SPLITR = false,
-          int SCHED = 6>
+template <int EPILOGUE, int BN_, bool TRA, bool TRB, bool SPLITR = false>
 __global__ __launch_bounds__(U_THREADS, 1)
 void gemm_uni_kernel(const short* __restrict__ A, const short* __restrict__ B,
                      const short* __restrict__ bias, short* __restrict__ C,
@@ -168,7 +157,6 @@ void gemm_uni_kernel(const short* __restrict__ A, const short* __restrict__ B,
   constexpr int A_ELEMS = BM_ * U_BK;
   constexpr int B_ELEMS = BN_ * U_BK;
   constexpr int SLOT = A_ELEMS + B_ELEMS;
-  constexpr int NB = BN_ / 64;          // B glds per thread per tile (4|2)
   extern __shared__ short smem[];
   const int lane = threadIdx.x & 63;
 
@@ -232,11 +220,8 @@ void gemm_uni_kernel(const short* __restrict__ A, const short* __restrict__ B,
   stage_a(0, 0, smem);
   stage_a(0, 1, smem);
   stage_b(0, smem + A_ELEMS);
-  U_WAIT_VM(0);
+  U_WAIT_VM0();
   U_BARRIER();
-
-  if (SCHED == 3 && __builtin_amdgcn_readfirstlane(threadIdx.x) >= 256)
-    __builtin_amdgcn_s_setprio(1);  // static young-half priority
 
   bf16x8u afr[MF / 2][2], bfr[NF][2];
 
@@ -252,15 +237,13 @@ void gemm_uni_kernel(const short* __restrict__ A, const short* __restrict__ B,
   };
 
 #define U_MFMA_QUAD(RH, CH)                                                \
-  if (SCHED == 0) __builtin_amdgcn_s_setprio(1);                          \
   _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                         \
     _Pragma("unroll") for (int i = 0; i < MF / 2; ++i)                     \
       _Pragma("unroll") for (int j = 0; j < NF / 2; ++j)                   \
         acc[(RH) * (MF / 2) + i][(CH) * (NF / 2) + j] =                    \
             __builtin_amdgcn_mfma_f32_16x16x32_bf16(                       \
                 afr[i][ks], bfr[(CH) * (NF / 2) + j][ks],                  \
-                acc[(RH) * (MF / 2) + i][(CH) * (NF / 2) + j], 0, 0, 0);   \
-  if (SCHED == 0) __builtin_amdgcn_s_setprio(0);
+                acc[(RH) * (MF / 2) + i][(CH) * (NF / 2) + j], 0, 0, 0);
 
   for (int t = 0; t < ntiles; ++t) {
     const short* a_lds = smem + (t & 1) * SLOT;
@@ -269,8 +252,7 @@ void gemm_uni_kernel(const short* __restrict__ A, const short* __restrict__ B,
     short* pb_lds = pa_lds + A_ELEMS;
     const bool do_pf = t + 1 < ntiles;
 
-    constexpr bool LOCKSTEP = (SCHED < 6);
-    // ---- q0: quadrant (0,0); issue t+1's A-piece0 + all B -------------
+    // ---- q0: quadrant (0,0); issue all of t+1's A and B ----------------
 #pragma unroll
     for (int i = 0; i < MF / 2; ++i)
 #pragma unroll
@@ -281,57 +263,33 @@ void gemm_uni_kernel(const short* __restrict__ A, const short* __restrict__ B,
       for (int ks = 0; ks < 2; ++ks) bfr[j][ks] = ldb_frag(j, ks, b_lds);
     if (do_pf) {
       stage_a(t + 1, 0, pa_lds);
-      if (SCHED != 4) stage_b(t + 1, pb_lds);
-      if (SCHED == 2 || SCHED >= 6) stage_a(t + 1, 1, pa_lds);
+      stage_b(t + 1, pb_lds);
+      stage_a(t + 1, 1, pa_lds);
     }
-    if (LOCKSTEP) U_BARRIER();
     U_WAIT_LGKM0();
     U_MFMA_QUAD(0, 0)
-    if (LOCKSTEP) U_BARRIER();
 
-    // ---- q1: quadrant (0,1); issue t+1's A-piece1 ---------------------
+    // ---- q1: quadrant (0,1) -------------------------------------------
 #pragma unroll
     for (int j = NF / 2; j < NF; ++j)
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) bfr[j][ks] = ldb_frag(j, ks, b_lds);
-    if (do_pf) {
-      if (SCHED == 4) stage_b(t + 1, pb_lds);
-      if (SCHED != 2 && SCHED < 6) stage_a(t + 1, 1, pa_lds);
-    }
-    if (LOCKSTEP) U_BARRIER();
     U_WAIT_LGKM0();
     U_MFMA_QUAD(0, 1)
-    // end-q1 wait: drain THIS tile's A-piece1 (issued q1 of t-1, 4 phases
-    // ago, consumed by q2's reads one barrier from here); t+1's
-    // A-piece0+B (2+NB) + A-piece1 (2) stay in flight.
-    if (SCHED != 2 && SCHED < 6) {
-      if (do_pf) {
-        if (BN_ == 256) U_WAIT_VM(8); else U_WAIT_VM(6);
-      } else {
-        U_WAIT_VM(0);
-      }
-    }
-    if (LOCKSTEP || SCHED == 7) U_BARRIER();
 
     // ---- q2: quadrant (1,0) -------------------------------------------
 #pragma unroll
     for (int i = 0; i < MF / 2; ++i)
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) afr[i][ks] = lda_frag(i, ks, 1, a_lds);
-    if (LOCKSTEP) U_BARRIER();
     U_WAIT_LGKM0();
     U_MFMA_QUAD(1, 0)
-    if (LOCKSTEP) U_BARRIER();
 
     // ---- q3: quadrant (1,1), operands already in registers ------------
     U_MFMA_QUAD(1, 1)
-    // end-q3 wait: drain t+1's A-piece0+B (issued q0, 3 phases ago);
-    // its A-piece1 (2 glds) stays in flight across the tile boundary.
-    if (SCHED == 2 || SCHED >= 6 || !do_pf) {
-      U_WAIT_VM(0);
-    } else {
-      U_WAIT_VM(2);
-    }
+    // tile boundary: t+1's loads (issued in q0, 3 phases ago) must have
+    // landed, and every wave must be done reading this tile's slot.
+    U_WAIT_VM0();
     U_BARRIER();
   }
 #undef U_MFMA_QUAD
@@ -483,226 +441,6 @@ static torch::Tensor gemm_uni_launch(
     long mn = (long)M * N;
     uni_reduce_kernel<<<(mn + 255) / 256, 256, 0, stream>>>(
         cwp, (short*)c.data_ptr(), mn, nslices);
-  }
-  return c;
-}
-
-// ---------------------------------------------------------------------------
-// Ring-schedule NT GEMM (SCHED=5 in the A/B): ONE LDS slot, half-granular
-// staging — each phase stages exactly one piece of tile t+1 into the
-// region the previous phase's readers just vacated (piece death points:
-// A-piece0 after q0's barrier, B after q1's, A-piece1 after q2's), with
-// two counted s_waitcnt vmcnt(2) per K-tile (end-q1 covers A-piece1 of
-// the CURRENT tile, end-q3 covers A-piece0+B of the NEXT) — the faithful
-// reconstruction of the guide's 8-phase example's load pipeline.  Halves
-// the LDS of the double-buffered schedule.
-// ---------------------------------------------------------------------------
-
-template <int EPILOGUE, int BN_, int WPS = 1>
-__global__ __launch_bounds__(U_THREADS, WPS)
-void gemm_ring_kernel(const short* __restrict__ A, const short* __restrict__ B,
-                      const short* __restrict__ bias, short* __restrict__ C,
-                      int M, int N, int K, long lda, long ldb, int has_bias,
-                      int nbm, int nbn) {
-  constexpr int BM_ = 256;
-  constexpr int MF = 8;
-  constexpr int NF = BN_ / 64;
-  constexpr int A_ELEMS = BM_ * U_BK;
-  extern __shared__ short smem[];
-  const int lane = threadIdx.x & 63;
-
-  int nwg = nbm * nbn;
-  int wg = blockIdx.x;
-  {
-    int q = nwg / 8, r = nwg % 8, x = wg % 8, o = wg / 8;
-    wg = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + o;
-  }
-  const int bm0 = (wg / nbn) * BM_;
-  const int bn0 = (wg % nbn) * BN_;
-
-  const int wid = threadIdx.x >> 6;
-  const int wm = (wid >> 2) * (BM_ / 2);
-  const int wn = (wid & 3) * (BN_ / 4);
-  const int fr = lane & 15;
-  const int kg = lane >> 4;
-
-  f32x4 acc[MF][NF];
-#pragma unroll
-  for (int i = 0; i < MF; ++i)
-#pragma unroll
-    for (int j = 0; j < NF; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
-
-  const int ntiles = K / U_BK;
-  short* a_lds = smem;
-  short* b_lds = smem + A_ELEMS;
-
-  auto stage_a = [&](int kt, int piece) {
-    u_stage_nt<256>(A + (long)kt * U_BK, lda, bm0, M, piece, a_lds);
-  };
-  auto stage_b = [&](int kt) {
-    if (BN_ == 256) {
-      u_stage_nt<256>(B + (long)kt * U_BK, ldb, bn0, N, 0, b_lds);
-      u_stage_nt<256>(B + (long)kt * U_BK, ldb, bn0, N, 1, b_lds);
-    } else {
-      u_stage_nt<128>(B + (long)kt * U_BK, ldb, bn0, N, 0, b_lds);
-    }
-  };
-
-  stage_a(0, 0);
-  stage_a(0, 1);
-  stage_b(0);
-  U_WAIT_VM(0);
-  U_BARRIER();
-
-  bf16x8u afr[MF / 2][2], bfr[NF][2];
-
-#define R_MFMA_QUAD(RH, CH)                                                \
-  _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                         \
-    _Pragma("unroll") for (int i = 0; i < MF / 2; ++i)                     \
-      _Pragma("unroll") for (int j = 0; j < NF / 2; ++j)                   \
-        acc[(RH) * (MF / 2) + i][(CH) * (NF / 2) + j] =                    \
-            __builtin_amdgcn_mfma_f32_16x16x32_bf16(                       \
-                afr[i][ks], bfr[(CH) * (NF / 2) + j][ks],                  \
-                acc[(RH) * (MF / 2) + i][(CH) * (NF / 2) + j], 0, 0, 0);
-
-  for (int t = 0; t < ntiles; ++t) {
-    const bool do_pf = t + 1 < ntiles;
-
-    // q0: read A-piece0 + B-low fragments; MFMA (0,0)
-#pragma unroll
-    for (int i = 0; i < MF / 2; ++i)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-        afr[i][ks] = u_frag_nt(a_lds, wm + i * 16 + fr, ks * 64 + kg * 16);
-#pragma unroll
-    for (int j = 0; j < NF / 2; ++j)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-        bfr[j][ks] = u_frag_nt(b_lds, wn + j * 16 + fr, ks * 64 + kg * 16);
-    U_BARRIER();
-    U_WAIT_LGKM0();
-    R_MFMA_QUAD(0, 0)
-    U_BARRIER();
-    // q1: stage A-piece0(t+1) into the region q0 vacated; read B-high
-    if (do_pf) stage_a(t + 1, 0);
-#pragma unroll
-    for (int j = NF / 2; j < NF; ++j)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-        bfr[j][ks] = u_frag_nt(b_lds, wn + j * 16 + fr, ks * 64 + kg * 16);
-    U_BARRIER();
-    U_WAIT_LGKM0();
-    R_MFMA_QUAD(0, 1)
-    // end-q1: drain THIS tile's A-piece1 (staged q3 of t-1); t+1's
-    // A-piece0 stays in flight
-    if (do_pf) U_WAIT_VM(2); else U_WAIT_VM(0);
-    U_BARRIER();
-    // q2: stage B(t+1) over the dead B regions; read A-piece1
-    if (do_pf) stage_b(t + 1);
-#pragma unroll
-    for (int i = 0; i < MF / 2; ++i)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-        afr[i][ks] = u_frag_nt(a_lds, wm + (BM_ / 4) + i * 16 + fr,
-                               ks * 64 + kg * 16);
-    U_BARRIER();
-    U_WAIT_LGKM0();
-    R_MFMA_QUAD(1, 0)
-    U_BARRIER();
-    // q3: stage A-piece1(t+1); MFMA (1,1) from registers
-    if (do_pf) stage_a(t + 1, 1);
-    R_MFMA_QUAD(1, 1)
-    // end-q3: drain t+1's A-piece0+B (2-3 phases in flight); its
-    // A-piece1 rides across the boundary (covered by next end-q1)
-    if (do_pf) U_WAIT_VM(2); else U_WAIT_VM(0);
-    U_BARRIER();
-  }
-#undef R_MFMA_QUAD
-
-#pragma unroll
-  for (int i = 0; i < MF; ++i) {
-    const int grow_base = bm0 + wm + i * 16 + kg * 4;
-#pragma unroll
-    for (int j = 0; j < NF; ++j) {
-      const int gcol = bn0 + wn + j * 16 + fr;
-      if (gcol >= N) continue;
-      const float bv = (has_bias && bias) ? bfbits2f(bias[gcol]) : 0.0f;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int grow = grow_base + r;
-        if (grow >= M) continue;
-        float v = acc[i][j][r] + bv;
-        if (EPILOGUE == 1) v = fmaxf(v, 0.0f);
-        C[(long)grow * N + gcol] = f2bfbits(v);
-      }
-    }
-  }
-}
-
-// Bench-only schedule A/B: NT x NT, no epilogue, BN=256 grid assumed.
-torch::Tensor gemm_uni_nt_ab(torch::Tensor a, torch::Tensor w,
-                             int64_t sched) {
-  const int M = a.size(0), K = a.size(1), N = w.size(0);
-  auto c = torch::empty({M, N}, a.options());
-  const int BN = ((long)cdiv(M, 256) * cdiv(N, 256) >= 224) ? 256 : 128;
-  const int nbm = cdiv(M, 256), nbn = cdiv(N, BN);
-  const size_t smem = 2 * ((size_t)256 + BN) * U_BK * sizeof(short);
-  auto stream = at::hip::getCurrentHIPStream();
-  auto go = [&](auto bnc, auto sc) {
-    constexpr int BNv = decltype(bnc)::value;
-    constexpr int SC = decltype(sc)::value;
-    auto kfn = gemm_uni_kernel<0, BNv, false, false, false, SC>;
-    (void)hipFuncSetAttribute((const void*)kfn,
-                              hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)smem);
-    kfn<<<nbm * nbn, U_THREADS, smem, stream>>>(
-        (const short*)a.data_ptr(), (const short*)w.data_ptr(), nullptr,
-        (short*)c.data_ptr(), nullptr, M, N, K, K, K, 0, nbm, nbn, K);
-  };
-  auto go2 = [&](auto sc) {
-    if (BN == 256) go(std::integral_constant<int, 256>{}, sc);
-    else go(std::integral_constant<int, 128>{}, sc);
-  };
-  if ((int)sched == 5) {
-    const size_t rsm = ((size_t)256 + BN) * U_BK * sizeof(short);
-    auto ring = [&](auto bnc) {
-      constexpr int BNv = decltype(bnc)::value;
-      auto kfn = gemm_ring_kernel<0, BNv>;
-      (void)hipFuncSetAttribute((const void*)kfn,
-                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)rsm);
-      kfn<<<nbm * nbn, U_THREADS, rsm, stream>>>(
-          (const short*)a.data_ptr(), (const short*)w.data_ptr(), nullptr,
-          (short*)c.data_ptr(), M, N, K, K, K, 0, nbm, nbn);
-    };
-    if (BN == 256) ring(std::integral_constant<int, 256>{});
-    else ring(std::integral_constant<int, 128>{});
-    return c;
-  }
-  if ((int)sched == 8) {
-    // ring @ BN128 with a 4-waves/SIMD VGPR cap: 48 KiB LDS + <=128
-    // VGPR admit TWO co-resident blocks per CU, overlapping prologue
-    // drains and boundary stalls across blocks (the K=512 1-block/CU
-    // shapes idle the CU during their prologue)
-    const int nbn8 = cdiv(N, 128);
-    const size_t rsm = ((size_t)256 + 128) * U_BK * sizeof(short);
-    auto kfn = gemm_ring_kernel<0, 128, 4>;
-    (void)hipFuncSetAttribute((const void*)kfn,
-                              hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)rsm);
-    kfn<<<nbm * nbn8, U_THREADS, rsm, stream>>>(
-        (const short*)a.data_ptr(), (const short*)w.data_ptr(), nullptr,
-        (short*)c.data_ptr(), M, N, K, K, K, 0, nbm, nbn8);
-    return c;
-  }
-  switch ((int)sched) {
-    case 0: go2(std::integral_constant<int, 0>{}); break;
-    case 2: go2(std::integral_constant<int, 2>{}); break;
-    case 3: go2(std::integral_constant<int, 3>{}); break;
-    case 4: go2(std::integral_constant<int, 4>{}); break;
-    case 6: go2(std::integral_constant<int, 6>{}); break;
-    case 7: go2(std::integral_constant<int, 7>{}); break;
-    default: go2(std::integral_constant<int, 1>{}); break;
   }
   return c;
 }

@@ -125,7 +125,7 @@ def refresh_weight_caches():
 # GEMM backend (round 2): every training-shape GEMM runs hand-written.
 # Forward goes to the gemm256/128 NT dispatch (measured best hand path:
 # 600-1040 TF; the uni counted-vmcnt schedule variants measured slower —
-# see gemm_uni.hip header); dX and the wide dW go to the gemm_uni TR-mode
+# see docs/PERF.md); dX and the wide dW go to the gemm_uni TR-mode
 # kernels (tr16 transpose-read operands).  hipBLASLt remains only as the
 # TFMX_FWD_GEMM=blaslt A/B arm; TFMX_FWD_GEMM=uni forces uni NT forward.
 _FWD_BACKEND = os.environ.get("TFMX_FWD_GEMM", "hand")
@@ -190,7 +190,7 @@ def _dw_gemm(dy, x, out=None):
     # zeroing — the fp32-atomic epilogue measured at the chip's atomic
     # rate); it sizes its own torch::empty workspace via the caching
     # allocator, so no Python-side workspace is needed.
-    return E.gemm_dw(dy.contiguous(), x, out, None, None)
+    return E.gemm_dw(dy.contiguous(), x, out, None)
 
 
 def _dw_db_gemm(dy, x, has_bias, w_out=None, b_out=None, db=None):
