@@ -4,7 +4,7 @@ serving side of that capability).
 
     python serve.py --model_dir model --src_vocab src_vocab.txt \
         --tgt_vocab tgt_vocab.txt [--device cuda] [--port 8000] \
-        [--fused_decode_attn]
+        [--fused_decode_attn] [--skinny_decode_linear [--skinny_decode_ln]]
 
 Endpoints:
     GET  /health               -> {"status": "ok", "config": {...}}
@@ -30,7 +30,9 @@ import torch
 
 def build_app(model_dir: str, src_vocab: str, tgt_vocab: str,
               device: str = "cpu", dtype=None,
-              fused_decode_attn: bool = False):
+              fused_decode_attn: bool = False,
+              skinny_decode_linear: bool = False,
+              skinny_decode_ln: bool = False):
     from fastapi import Body, FastAPI
 
     from transformer_amd.runtime.export import load_exported
@@ -69,7 +71,9 @@ def build_app(model_dir: str, src_vocab: str, tgt_vocab: str,
                 model, B=1, S_src=key[0], max_len=key[1],
                 start_id=tgt_tok.vocab_size,
                 device=next(model.parameters()).device,
-                fused_attn=fused_decode_attn)
+                fused_attn=fused_decode_attn,
+                skinny_linear=skinny_decode_linear,
+                skinny_ln=skinny_decode_ln)
         return graphed[key], key[0]
 
     app = FastAPI(title="transformer_amd", version="1.0")
@@ -101,7 +105,9 @@ def build_app(model_dir: str, src_vocab: str, tgt_vocab: str,
             else:
                 out = greedy_decode(model, enc_in, tgt_start, tgt_start + 1,
                                     max_len=max_len,
-                                    fused_attn=fused_decode_attn)
+                                    fused_attn=fused_decode_attn,
+                                    skinny_linear=skinny_decode_linear,
+                                    skinny_ln=skinny_decode_ln)
         ids = out.squeeze(0).tolist()
         body = [t for t in ids if 0 < t < tgt_tok.vocab_size]
         return {"tokens": ids, "text": tgt_tok.decode(body)}
@@ -121,13 +127,22 @@ def main(argv=None):
     p.add_argument("--fused_decode_attn", action="store_true",
                    help="decode with the single-query split-KV attention "
                         "kernels (fused KV append); off by default")
+    p.add_argument("--skinny_decode_linear", action="store_true",
+                   help="decode with the one-launch skinny-M linear kernel "
+                        "in place of the training GEMM; off by default")
+    p.add_argument("--skinny_decode_ln", action="store_true",
+                   help="with --skinny_decode_linear: run the linears that "
+                        "feed a LayerNorm fused with it, one launch each "
+                        "(measured slower than two launches; off by default)")
     args = p.parse_args(argv)
 
     import uvicorn
     app = build_app(args.model_dir, args.src_vocab, args.tgt_vocab,
                     args.device,
                     torch.bfloat16 if args.device.startswith("cuda") else None,
-                    fused_decode_attn=args.fused_decode_attn)
+                    fused_decode_attn=args.fused_decode_attn,
+                    skinny_decode_linear=args.skinny_decode_linear,
+                    skinny_decode_ln=args.skinny_decode_ln)
     uvicorn.run(app, host=args.host, port=args.port)
 
 

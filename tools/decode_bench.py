@@ -1,14 +1,18 @@
 """Serving decode latency: eager KV-cached loop vs hipGraph-captured decoder
-vs the captured decoder on the single-query decode-attention kernels.
+vs the captured decoder on the single-query decode-attention kernels vs the
+same with the one-launch skinny decode linears as well.
 
 Transformer-base, greedy decode.  The eager loop is launch-bound at small
 batch (hundreds of kernel launches per token); GraphedDecoder replays one
 captured graph per token; with fused_attn=True each attention of the
-captured step is one split-KV launch that also appends the K/V row.
+captured step is one split-KV launch that also appends the K/V row; with
+skinny_linear=True each linear of the step is one linear_rows launch, and
+with skinny_ln=True as well the three per layer that feed a LayerNorm run
+fused with it.
 
     python tools/decode_bench.py [--reps N] [--long] [--no_eager]
 
---reps N  time each graphed decoder N times, alternating the two, and print
+--reps N  time each graphed decoder N times, alternating them, and print
           the median and the min..max spread of ms/token
 --long    add the long-context point B=1, S_src=64, L=2048
 """
@@ -75,21 +79,30 @@ for B, S, L in configs:
         eager = f"eager {te*1e3/n_e:.2f} ms/tok ({B*n_e/te:.0f} tok/s) | "
 
     decs = [GraphedDecoder(m, B=B, S_src=S, max_len=L, start_id=START,
-                           device=torch.device("cuda"), fused_attn=f)
-            for f in (False, True)]
+                           device=torch.device("cuda"), fused_attn=f,
+                           skinny_linear=k, skinny_ln=n)
+            for f, k, n in ((False, False, False), (True, False, False),
+                            (True, True, False), (True, True, True))]
     for d in decs:
         d(inp, END, max_len=8)  # warm
-    ts, outs = ([], []), [None, None]
+    ts, outs = ([], [], [], []), [None] * 4
     for _ in range(args.reps):
         for i, d in enumerate(decs):
             outs[i], t = timed(lambda: d(inp, END, max_len=L))
             ts[i].append(t)
     ok = same_until_end(outs[0], outs[1])
+    ok_s = same_until_end(outs[0], outs[2])
+    ok_n = same_until_end(outs[0], outs[3])
     if not args.no_eager:
         ok = ok and same_until_end(out_e, outs[0])
-    tg, tf = statistics.median(ts[0]), statistics.median(ts[1])
+    tg, tf, tk, tn = (statistics.median(t) for t in ts)
     print(f"B={B} S={S} L={L}: {eager}graphed {stats(ts[0], L)} ms/tok "
           f"({B*L/tg:.0f} tok/s) | graphed+fused_attn {stats(ts[1], L)} "
           f"ms/tok ({B*L/tf:.0f} tok/s) | fused/graphed time {tf/tg:.3f} "
-          f"| parity {'OK' if ok else 'MISMATCH'}", flush=True)
+          f"| parity {'OK' if ok else 'MISMATCH'} | +skinny_linear "
+          f"{stats(ts[2], L)} ms/tok ({B*L/tk:.0f} tok/s) | skinny/fused "
+          f"time {tk/tf:.3f} | tokens vs graphed "
+          f"{'same' if ok_s else 'DIFFER'} | +skinny_ln "
+          f"{stats(ts[3], L)} ms/tok | skinny_ln/skinny time {tn/tk:.3f} "
+          f"| tokens vs graphed {'same' if ok_n else 'DIFFER'}", flush=True)
 print("decode bench done")

@@ -338,7 +338,8 @@ class DecodeCache:
 
     def __init__(self, model: "Transformer", B: int, max_len: int,
                  enc_output: torch.Tensor, src_pad: torch.Tensor,
-                 fused_attn: bool = False):
+                 fused_attn: bool = False, skinny_linear: bool = False,
+                 skinny_ln: bool = False):
         dec = model.decoder
         d = dec.d_model
         layer0 = dec.layers[0]
@@ -363,6 +364,12 @@ class DecodeCache:
             self.kv_len = torch.zeros(B, dtype=torch.int32, device=dev)
             self.ws = ops.decode_attention_workspace(B, H, dh,
                                                      max(max_len, Sk), dev)
+        # skinny_linear: the step's linears run ops.linear_rows; skinny_ln:
+        # the three per layer that feed a LayerNorm run the fused variant
+        # and share one fp32 workspace
+        self.skinny_linear = skinny_linear
+        self.lin_ws = (ops.linear_rows_workspace(B, d, dev)
+                       if skinny_linear and skinny_ln else None)
 
 
 @torch.no_grad()
@@ -370,6 +377,23 @@ def encode(model, inp, training=False):
     """Run the encoder once; returns (enc_output, src_pad)."""
     src_pad = (inp == 0).to(torch.uint8)
     return model.encoder(inp, src_pad, training), src_pad
+
+
+def _step_linears(skinny: bool, ln_ws=None):
+    """(lin, lin_ln) for one decoder step.  lin(x, w, b, activation=None) is
+    a linear: the one-launch decode kernel (ops.linear_rows) when skinny,
+    else the training GEMM.  lin_ln(x, w, b, res, ln) = LN(lin(x) + res):
+    with a workspace ln_ws (skinny only) one launch of the fused variant,
+    else lin followed by the residual LayerNorm kernel."""
+    lin = ops.linear_rows if skinny else ops.linear
+
+    def lin_ln(x, w, b, res, ln):
+        if ln_ws is not None:
+            return ops.linear_rows_residual_layernorm(
+                x, w, b, res, ln.gamma, ln.beta, ln.eps, ln_ws)
+        return ops.residual_layernorm(lin(x, w, b), res, ln.gamma, ln.beta,
+                                      ln.eps)
+    return lin, lin_ln
 
 
 @torch.no_grad()
@@ -381,13 +405,14 @@ def decode_step(model, tokens_new, cache: DecodeCache):
     dec = model.decoder
     B = tokens_new.shape[0]
     t = cache.pos
+    lin, lin_ln = _step_linears(cache.skinny_linear, cache.lin_ws)
     # embedding * sqrt(d) + PE at position t
     x = ops.embedding_scale_pe_at(tokens_new, dec.embedding, dec.pe, t)
     for li, layer in enumerate(dec.layers):
         H, dh = layer.mha1.num_heads, layer.mha1.depth
         # masked self-attention against the cache: project packed qkv for the
         # new row, append k/v in place, attend over positions [0, t].
-        qkv = ops.linear(x, layer.mha1.w_qkv, layer.mha1.b_qkv)
+        qkv = lin(x, layer.mha1.w_qkv, layer.mha1.b_qkv)
         qkv = qkv.view(B, 1, 3, H, dh)
         if cache.kv_len is not None:
             attn1 = ops.decode_attention_self(qkv, cache.self_kv[li],
@@ -398,12 +423,10 @@ def decode_step(model, tokens_new, cache: DecodeCache):
             kv_hist = cache.self_kv[li][:, :t + 1]
             k, v = kv_hist.unbind(dim=2)
             attn1 = ops.fused_attention(q, k, v)  # all cached keys visible
-        attn1 = ops.linear(attn1.reshape(B, 1, H * dh),
-                           layer.mha1.w_o, layer.mha1.b_o)
-        out1 = ops.residual_layernorm(attn1, x, layer.ln1.gamma,
-                                      layer.ln1.beta, layer.ln1.eps)
+        out1 = lin_ln(attn1.reshape(B, 1, H * dh), layer.mha1.w_o,
+                      layer.mha1.b_o, x, layer.ln1)
         # cross-attention against precomputed encoder K/V
-        q2 = ops.linear(out1, layer.mha2.w_q, layer.mha2.b_q)
+        q2 = lin(out1, layer.mha2.w_q, layer.mha2.b_q)
         q2 = q2.view(B, 1, H, dh)
         if cache.kv_len is not None:
             attn2 = ops.decode_attention_cross(q2, cache.cross_kv[li],
@@ -411,30 +434,33 @@ def decode_step(model, tokens_new, cache: DecodeCache):
         else:
             k2, v2 = cache.cross_kv[li].unbind(dim=2)
             attn2 = ops.fused_attention(q2, k2, v2, kv_pad=cache.src_pad)
-        attn2 = ops.linear(attn2.reshape(B, 1, H * dh),
-                           layer.mha2.w_o, layer.mha2.b_o)
-        out2 = ops.residual_layernorm(attn2, out1, layer.ln2.gamma,
-                                      layer.ln2.beta, layer.ln2.eps)
-        ffn = layer.ffn(out2)
-        x = ops.residual_layernorm(ffn, out2, layer.ln3.gamma,
-                                   layer.ln3.beta, layer.ln3.eps)
+        out2 = lin_ln(attn2.reshape(B, 1, H * dh), layer.mha2.w_o,
+                      layer.mha2.b_o, out1, layer.ln2)
+        ffn = layer.ffn
+        h = lin(out2, ffn.w1, ffn.b1, activation="relu")
+        x = lin_ln(h, ffn.w2, ffn.b2, out2, layer.ln3)
     cache.pos = t + 1
     if cache.kv_len is not None:
         cache.kv_len.add_(1)
-    return ops.linear(x, model.w_final, model.b_final)
+    return lin(x, model.w_final, model.b_final)
 
 
 @torch.no_grad()
 def greedy_decode(model, inp, start_id, end_id, max_len=10,
-                  fused_attn=False):
+                  fused_attn=False, skinny_linear=False, skinny_ln=False):
     """KV-cached greedy decode.  inp (B, S) int64; returns (B, <=max_len+1)
     token ids starting with start_id; stops early when every sequence has
     emitted end_id.  fused_attn: the single-query decode-attention kernels
-    (ops.decode_attention_self/_cross) in place of the training kernel."""
+    (ops.decode_attention_self/_cross) in place of the training kernel.
+    skinny_linear: the one-launch decode linear (ops.linear_rows) in place
+    of the training GEMM; composes with fused_attn.  skinny_ln (with
+    skinny_linear): the linears that feed a LayerNorm run fused with it
+    (ops.linear_rows_residual_layernorm)."""
     B = inp.shape[0]
     enc_output, src_pad = encode(model, inp)
     cache = DecodeCache(model, B, max_len + 1, enc_output, src_pad,
-                        fused_attn=fused_attn)
+                        fused_attn=fused_attn, skinny_linear=skinny_linear,
+                        skinny_ln=skinny_ln)
     out = torch.full((B, 1), start_id, dtype=torch.int64, device=inp.device)
     finished = torch.zeros(B, dtype=torch.bool, device=inp.device)
     for _ in range(max_len):
@@ -475,11 +501,16 @@ class GraphedDecoder:
 
     @torch.no_grad()
     def __init__(self, model: "Transformer", B: int, S_src: int, max_len: int,
-                 start_id: int, device, fused_attn: bool = False):
+                 start_id: int, device, fused_attn: bool = False,
+                 skinny_linear: bool = False, skinny_ln: bool = False):
         """fused_attn: the captured step runs ops.decode_attention_self /
         _cross (append + attention in one launch each, over an int32 (B,)
         device length) in place of the pad-mask unmask, the cache
-        index_copy_, the query copy and the training attention kernel."""
+        index_copy_, the query copy and the training attention kernel.
+        skinny_linear: every linear of the captured step is one
+        ops.linear_rows launch (no split-K fill/finalize); skinny_ln
+        (with skinny_linear): w_o, the cross w_o and ffn.w2 run fused with
+        the residual LayerNorm that follows them, one launch each."""
         assert max_len >= 4, "warmup+capture advance the position past 3"
         self.model = model
         self.B, self.S_src, self.max_len = B, S_src, max_len
@@ -493,6 +524,11 @@ class GraphedDecoder:
                                       dtype=dt)
         self.src_pad = torch.zeros(B, S_src, dtype=torch.uint8, device=device)
         self.fused_attn = fused_attn
+        # allocated here, outside capture, and kept on self: the captured
+        # graph holds its address for every replay
+        self.lin_ws = (ops.linear_rows_workspace(B, dec.d_model, device)
+                       if skinny_linear and skinny_ln else None)
+        lin, lin_ln = _step_linears(skinny_linear, self.lin_ws)
         # fused path: rows past kv_len are never read, so no zero-fill
         self.self_kv = [(torch.empty if fused_attn else torch.zeros)(
             B, max_len, 2, H, dh, device=device, dtype=dt)
@@ -522,7 +558,7 @@ class GraphedDecoder:
             # same kernel as the eager decode path -> bit-identical tokens
             x = O.ext().embed_pe_fwd(cur, dec.embedding, pe_row)
             for li, layer in enumerate(dec.layers):
-                qkv = O.linear(x, layer.mha1.w_qkv, layer.mha1.b_qkv)
+                qkv = lin(x, layer.mha1.w_qkv, layer.mha1.b_qkv)
                 qkv = qkv.view(B, 1, 3, H, dh)
                 if fused_attn:
                     attn1 = O.decode_attention_self(qkv, self.self_kv[li],
@@ -532,11 +568,9 @@ class GraphedDecoder:
                     q = qkv[:, :, 0].contiguous()
                     k, v = self.self_kv[li].unbind(dim=2)
                     attn1 = O.fused_attention(q, k, v, kv_pad=self.kv_pad)
-                attn1 = O.linear(attn1.reshape(B, 1, H * dh),
-                                 layer.mha1.w_o, layer.mha1.b_o)
-                out1 = O.residual_layernorm(attn1, x, layer.ln1.gamma,
-                                            layer.ln1.beta, layer.ln1.eps)
-                q2 = O.linear(out1, layer.mha2.w_q, layer.mha2.b_q)
+                out1 = lin_ln(attn1.reshape(B, 1, H * dh), layer.mha1.w_o,
+                              layer.mha1.b_o, x, layer.ln1)
+                q2 = lin(out1, layer.mha2.w_q, layer.mha2.b_q)
                 q2 = q2.view(B, 1, H, dh)
                 if fused_attn:
                     attn2 = O.decode_attention_cross(q2, self.cross_kv[li],
@@ -545,14 +579,12 @@ class GraphedDecoder:
                     k2, v2 = self.cross_kv[li].unbind(dim=2)
                     attn2 = O.fused_attention(q2, k2, v2,
                                               kv_pad=self.src_pad)
-                attn2 = O.linear(attn2.reshape(B, 1, H * dh),
-                                 layer.mha2.w_o, layer.mha2.b_o)
-                out2 = O.residual_layernorm(attn2, out1, layer.ln2.gamma,
-                                            layer.ln2.beta, layer.ln2.eps)
-                ffn = layer.ffn(out2)
-                x = O.residual_layernorm(ffn, out2, layer.ln3.gamma,
-                                         layer.ln3.beta, layer.ln3.eps)
-            logits = O.linear(x, self.model.w_final, self.model.b_final)
+                out2 = lin_ln(attn2.reshape(B, 1, H * dh), layer.mha2.w_o,
+                              layer.mha2.b_o, out1, layer.ln2)
+                ffn = layer.ffn
+                h = lin(out2, ffn.w1, ffn.b1, activation="relu")
+                x = lin_ln(h, ffn.w2, ffn.b2, out2, layer.ln3)
+            logits = lin(x, self.model.w_final, self.model.b_final)
             nxt = O.argmax_lastdim(logits).view(B, 1)
             self.tok.index_copy_(1, pos + 1, nxt)
             self.pos.add_(1)

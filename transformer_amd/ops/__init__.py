@@ -55,6 +55,9 @@ from .functional import (  # noqa: E402
     decode_attention_self,
     decode_attention_cross,
     decode_attention_workspace,
+    linear_rows,
+    linear_rows_residual_layernorm,
+    linear_rows_workspace,
     residual_layernorm,
     dropout_residual_layernorm,
     linear_dropout_residual_layernorm,

@@ -80,6 +80,16 @@ torch::Tensor decode_attn_workspace(int64_t B, int64_t H, int64_t dh,
                                     int64_t L);
 int64_t decode_attn_nsplit(int64_t BH, int64_t L);
 
+torch::Tensor linear_rows(torch::Tensor x, torch::Tensor w,
+                          c10::optional<torch::Tensor> bias, bool relu,
+                          int64_t nw);
+torch::Tensor linear_rows_ln(torch::Tensor x, torch::Tensor w,
+                             c10::optional<torch::Tensor> bias,
+                             torch::Tensor res, torch::Tensor gamma,
+                             torch::Tensor beta, double eps, torch::Tensor ws,
+                             int64_t nw);
+torch::Tensor linear_rows_workspace(int64_t M, int64_t N);
+
 torch::Tensor embed_pe_fwd(torch::Tensor tokens, torch::Tensor weight,
                            torch::Tensor pe,
                            c10::optional<torch::Tensor> positions);
@@ -255,6 +265,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("decode_attn_nsplit", &decode_attn_nsplit,
         "the host rule's split count for B*H rows and a key window of L",
         pybind11::arg("BH"), pybind11::arg("L"));
+  m.def("linear_rows", &linear_rows,
+        "Y[M,N] = X[M,K] @ W[N,K]^T (+bias)(+ReLU) for 1 <= M <= 64 in one "
+        "launch: no workspace, no atomics, fixed summation order.  K % 8 == "
+        "0, x and w contiguous and 16-byte aligned.  nw 0 = host rule, else "
+        "4 or 8 waves per block (sweeps)",
+        pybind11::arg("x"), pybind11::arg("w"),
+        pybind11::arg("bias") = pybind11::none(),
+        pybind11::arg("relu") = false, pybind11::arg("nw") = 0);
+  m.def("linear_rows_ln", &linear_rows_ln,
+        "LayerNorm(X @ W^T + bias + res; gamma, beta, eps) in one launch, "
+        "pre-norm values kept in fp32; N <= 2048; ws from "
+        "linear_rows_workspace",
+        pybind11::arg("x"), pybind11::arg("w"), pybind11::arg("bias"),
+        pybind11::arg("res"), pybind11::arg("gamma"), pybind11::arg("beta"),
+        pybind11::arg("eps"), pybind11::arg("ws"), pybind11::arg("nw") = 0);
+  m.def("linear_rows_workspace", &linear_rows_workspace,
+        "zeroed ticket + fp32 (M,N) pre-norm rows for linear_rows_ln; "
+        "allocate once outside graph capture, share per stream only",
+        pybind11::arg("M"), pybind11::arg("N"));
   m.def("embed_pe_fwd", &embed_pe_fwd, pybind11::arg("tokens"),
         pybind11::arg("weight"), pybind11::arg("pe"),
         pybind11::arg("positions") = pybind11::none());

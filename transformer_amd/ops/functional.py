@@ -656,6 +656,75 @@ def dropout_residual_layernorm(x, res, gamma, beta, rate: float,
 
 
 # ---------------------------------------------------------------------------
+# Skinny-M decode linears (forward only, csrc/linear_rows.hip): one launch
+# per linear for 1 <= M <= 64 rows, and one launch for a linear together
+# with the residual add + LayerNorm that follows it.
+# ---------------------------------------------------------------------------
+
+def linear_rows_workspace(M, N, device=None):
+    """Scratch for linear_rows_residual_layernorm calls of at most M rows
+    and N output columns.  Allocate it once, outside graph capture, and keep
+    it alive as long as a graph that captured it; the layers of a step may
+    share it because their calls are stream-ordered, but calls on different
+    streams must not.  CPU: an empty placeholder."""
+    dev = torch.device(device if device is not None else
+                       ("cuda" if torch.cuda.is_available() else "cpu"))
+    if dev.type != "cuda":
+        return torch.zeros(0)
+    with torch.cuda.device(dev):
+        return ext().linear_rows_workspace(M, N)
+
+
+def _vec_ok(t, n):
+    return t is None or (t.is_cuda and t.dtype == torch.bfloat16
+                         and t.is_contiguous() and t.numel() == n)
+
+
+def _rows_kernel_ok(x2, w, b):
+    """What csrc/linear_rows.hip serves; anything else is ops.linear's.
+    At more than 32 rows every block re-reads a 4-group X from L2, and the
+    kernel measured slower than gemm_nt on the deep (K >= 2048) and the wide
+    (32k head) shapes (docs/PERF.md), so those stay on the GEMM too."""
+    if not (x2.is_cuda and w.is_cuda and w.dim() == 2
+            and x2.dtype == w.dtype == torch.bfloat16 and w.is_contiguous()):
+        return False
+    M, K = x2.shape
+    N = w.shape[0]
+    if not (1 <= M <= 64 and K == w.shape[1] and K >= 8 and K % 8 == 0
+            and x2.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0
+            and _vec_ok(b, N)):
+        return False
+    return M <= 32 or (K < 2048 and N <= 4096)
+
+
+def linear_rows(x, w, b=None, activation=None):
+    """y = x @ W^T + b (+ReLU) for decode-sized inputs (at most 64 rows
+    after flattening the leading dims): one launch, fixed summation order.
+    Forward only.  Shapes or layouts the kernel does not serve, and CPU
+    tensors, go through ops.linear."""
+    x2 = x.reshape(-1, x.shape[-1]).contiguous()
+    if not _rows_kernel_ok(x2, w, b):
+        return linear(x, w, b, activation)
+    y = ext().linear_rows(x2, w, b, activation == "relu")
+    return y.view(*x.shape[:-1], w.shape[0])
+
+
+def linear_rows_residual_layernorm(x, w, b, res, gamma, beta, eps, ws):
+    """LN(x @ W^T + b + res) in one launch; the linear's output stays fp32
+    up to the LayerNorm.  ws: linear_rows_workspace.  Forward only; falls
+    back to residual_layernorm(linear(..)) where linear_rows falls back, and
+    for more than 2048 output columns."""
+    x2 = x.reshape(-1, x.shape[-1]).contiguous()
+    N = w.shape[0]
+    if not (_rows_kernel_ok(x2, w, b) and N <= 2048 and _vec_ok(gamma, N)
+            and _vec_ok(beta, N) and res.dtype == torch.bfloat16
+            and ws.numel() >= 4 + x2.shape[0] * N):
+        return residual_layernorm(linear(x, w, b), res, gamma, beta, eps)
+    y = ext().linear_rows_ln(x2, w, b, _rows(res), gamma, beta, eps, ws)
+    return y.view(res.shape)
+
+
+# ---------------------------------------------------------------------------
 # Fused embedding * sqrt(d) + positional encoding (K10).
 # ---------------------------------------------------------------------------
 
