@@ -4,12 +4,21 @@ serving side of that capability).
 
     python serve.py --model_dir model --src_vocab src_vocab.txt \
         --tgt_vocab tgt_vocab.txt [--device cuda] [--port 8000] \
-        [--fused_decode_attn] [--skinny_decode_linear [--skinny_decode_ln]]
+        [--fused_decode_attn] [--skinny_decode_linear [--skinny_decode_ln]] \
+        [--beam_size N [--length_penalty A]]
 
 Endpoints:
     GET  /health               -> {"status": "ok", "config": {...}}
-    POST /translate            {"text": "...", "max_len": 10}
-                               -> {"tokens": [...], "text": "..."}
+    POST /translate            {"text": "...", "max_len": 10, "beam_size": 4}
+                               -> {"tokens": [...], "text": "...",
+                                   "score": -1.23}
+
+"beam_size" is optional (default --beam_size, clamped to [1, 8]).  Above 1
+the request runs beam search (models/transformer.py beam_search_decode: the
+beam kernels of csrc/beam_search.hip, eager, honouring
+--skinny_decode_linear) and returns the best hypothesis with its cumulative
+log-prob as "score"; at 1 "score" is null and the greedy paths below run
+exactly as without the option.
 
 Greedy KV-cached decode (models/transformer.py greedy_decode); the decode
 runs under torch.no_grad on whatever device the model was loaded to.  On
@@ -32,12 +41,14 @@ def build_app(model_dir: str, src_vocab: str, tgt_vocab: str,
               device: str = "cpu", dtype=None,
               fused_decode_attn: bool = False,
               skinny_decode_linear: bool = False,
-              skinny_decode_ln: bool = False):
+              skinny_decode_ln: bool = False, beam_size: int = 1,
+              length_penalty: float = 0.0):
     from fastapi import Body, FastAPI
 
     from transformer_amd.runtime.export import load_exported
     from transformer_amd.data.tokenizer import SubwordTokenizer
     from transformer_amd.models.transformer import (GraphedDecoder,
+                                                    beam_search_decode,
                                                     greedy_decode)
 
     model, config = load_exported(model_dir, device=device, dtype=dtype)
@@ -94,8 +105,18 @@ def build_app(model_dir: str, src_vocab: str, tgt_vocab: str,
         enc_in = torch.tensor([tokens], dtype=torch.int64,
                               device=next(model.parameters()).device)
         tgt_start = tgt_tok.vocab_size
+        beams = clamp_beam_size(payload.get("beam_size", beam_size))
+        score = None
         with torch.no_grad():
-            if use_graph:
+            if beams > 1:
+                with graph_lock:
+                    hyps, scores = beam_search_decode(
+                        model, enc_in, tgt_start, tgt_start + 1,
+                        beam_size=beams, max_len=max_len,
+                        length_penalty=length_penalty,
+                        skinny_linear=skinny_decode_linear)
+                out, score = hyps[:, 0], float(scores[0, 0])
+            elif use_graph:
                 with graph_lock:
                     dec, s_bucket = get_graphed(len(tokens), max_len)
                     padded = torch.zeros(1, s_bucket, dtype=torch.int64,
@@ -110,12 +131,17 @@ def build_app(model_dir: str, src_vocab: str, tgt_vocab: str,
                                     skinny_ln=skinny_decode_ln)
         ids = out.squeeze(0).tolist()
         body = [t for t in ids if 0 < t < tgt_tok.vocab_size]
-        return {"tokens": ids, "text": tgt_tok.decode(body)}
+        return {"tokens": ids, "text": tgt_tok.decode(body), "score": score}
 
     return app
 
 
-def main(argv=None):
+def clamp_beam_size(n) -> int:
+    """Beam sizes the beam kernels serve: [1, 8]."""
+    return min(max(int(n), 1), 8)
+
+
+def parse_args(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--model_dir", type=str, default="model")
     p.add_argument("--src_vocab", type=str, default="src_vocab.txt")
@@ -134,7 +160,16 @@ def main(argv=None):
                    help="with --skinny_decode_linear: run the linears that "
                         "feed a LayerNorm fused with it, one launch each "
                         "(measured slower than two launches; off by default)")
-    args = p.parse_args(argv)
+    p.add_argument("--beam_size", type=int, default=1,
+                   help="default beams per request (a request's \"beam_size\" "
+                        "overrides it; clamped to [1, 8]); 1 = greedy")
+    p.add_argument("--length_penalty", type=float, default=0.0,
+                   help="beam search ranks by score / ((5+len)/6)**this")
+    return p.parse_args(argv)
+
+
+def main(argv=None):
+    args = parse_args(argv)
 
     import uvicorn
     app = build_app(args.model_dir, args.src_vocab, args.tgt_vocab,
@@ -142,7 +177,9 @@ def main(argv=None):
                     torch.bfloat16 if args.device.startswith("cuda") else None,
                     fused_decode_attn=args.fused_decode_attn,
                     skinny_decode_linear=args.skinny_decode_linear,
-                    skinny_decode_ln=args.skinny_decode_ln)
+                    skinny_decode_ln=args.skinny_decode_ln,
+                    beam_size=args.beam_size,
+                    length_penalty=args.length_penalty)
     uvicorn.run(app, host=args.host, port=args.port)
 
 

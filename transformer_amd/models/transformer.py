@@ -339,7 +339,7 @@ class DecodeCache:
     def __init__(self, model: "Transformer", B: int, max_len: int,
                  enc_output: torch.Tensor, src_pad: torch.Tensor,
                  fused_attn: bool = False, skinny_linear: bool = False,
-                 skinny_ln: bool = False):
+                 skinny_ln: bool = False, second_kv: bool = False):
         dec = model.decoder
         d = dec.d_model
         layer0 = dec.layers[0]
@@ -351,6 +351,15 @@ class DecodeCache:
         self.src_pad = src_pad
         self.self_kv = [torch.empty(B, max_len, 2, H, dh, device=dev, dtype=dt)
                         for _ in dec.layers]
+        # second_kv (beam search): the set the cache reorder gathers INTO,
+        # swapped with self_kv after every step, and one pointer table per
+        # direction for ops.beam_gather_kv
+        self.self_kv_alt = self.gather_tables = None
+        if second_kv:
+            self.self_kv_alt = [torch.empty_like(t) for t in self.self_kv]
+            self.gather_tables = [
+                ops.beam_gather_table(self.self_kv, self.self_kv_alt),
+                ops.beam_gather_table(self.self_kv_alt, self.self_kv)]
         # cross K/V once per sequence (B, Sk, 2, H, dh)
         self.cross_kv = []
         Sk = enc_output.shape[1]
@@ -483,6 +492,67 @@ def mask_after_end(out: torch.Tensor, end_id: int) -> torch.Tensor:
     mask[:, 0] = False
     out[mask] = 0
     return out
+
+
+@torch.no_grad()
+def beam_search_decode(model, inp, start_id, end_id, beam_size=4, max_len=10,
+                       length_penalty=0.0, skinny_linear=False):
+    """KV-cached beam search.  inp (B, S) int64.  Returns (hyps, scores):
+    hyps (B, K, <=max_len+1) int64 starting with start_id, tokens after the
+    first end_id zeroed; scores (B, K) fp32 cumulative log-probs; both
+    sorted best first by score / ((5+len)/6)**length_penalty (0: the raw
+    log-prob).  The B*K hypotheses are the rows of one DecodeCache
+    (fused_attn) with two self-attention cache sets.  Per step: decode_step,
+    ops.beam_topk (selection), ops.beam_gather_kv (each survivor's K/V
+    history to its new row, from one set into the other), swap the sets.
+    A finished hypothesis keeps its slot and its score and is fed token 0;
+    all per-step state stays on the device, and the host reads one flag per
+    step to stop when every beam is finished."""
+    K = int(beam_size)
+    assert 1 <= K <= 8, "beam_size must be in [1, 8]"
+    B, dev = inp.shape[0], inp.device
+    enc_output, src_pad = encode(model, inp)
+    cache = DecodeCache(model, B * K, max_len + 1,
+                        enc_output.repeat_interleave(K, dim=0),
+                        src_pad.repeat_interleave(K, dim=0), fused_attn=True,
+                        skinny_linear=skinny_linear, second_kv=True)
+    ws = ops.beam_search_workspace(B, K, model.w_final.shape[0], dev)
+    scores = torch.full((B, K), float("-inf"), device=dev)
+    scores[:, 0] = 0.0                      # one live beam per sentence
+    finished = torch.zeros(B, K, dtype=torch.uint8, device=dev)
+    lens = torch.zeros(B, K, dtype=torch.int32, device=dev)
+    tok = torch.full((B * K, 1), start_id, dtype=torch.int64, device=dev)
+    tok_hist = torch.zeros(max_len, B, K, dtype=torch.int64, device=dev)
+    par_hist = torch.zeros(max_len, B, K, dtype=torch.int64, device=dev)
+    # keys cached per row BEFORE the step (decode_step advances its own
+    # count on the way out): what beam_gather_kv's "+1" is relative to
+    kv_before = torch.zeros(B * K, dtype=torch.int32, device=dev)
+    T = 0
+    for t in range(max_len):
+        logits = decode_step(model, tok, cache)
+        tok, parent, src_row, scores, finished, lens = ops.beam_topk(
+            logits, scores, finished, lens, end_id, ws)
+        ops.beam_gather_kv(cache.self_kv, cache.self_kv_alt, src_row,
+                           kv_before, cache.gather_tables[t % 2])
+        cache.self_kv, cache.self_kv_alt = cache.self_kv_alt, cache.self_kv
+        kv_before.add_(1)
+        tok_hist[t] = tok.view(B, K)
+        par_hist[t] = parent
+        T = t + 1
+        if bool(finished.all()):
+            break
+    # backtrack through the parents, last step first
+    hyps = torch.zeros(B, K, T + 1, dtype=torch.int64, device=dev)
+    hyps[:, :, 0] = start_id
+    idx = torch.arange(K, device=dev).expand(B, K)
+    for t in reversed(range(T)):
+        hyps[:, :, t + 1] = tok_hist[t].gather(1, idx)
+        idx = par_hist[t].gather(1, idx)
+    hyps = mask_after_end(hyps.view(B * K, T + 1), end_id).view(B, K, T + 1)
+    norm = scores / ((5.0 + lens.float()) / 6.0) ** float(length_penalty)
+    order = torch.sort(norm, dim=1, descending=True, stable=True).indices
+    hyps = hyps.gather(1, order[:, :, None].expand(B, K, T + 1))
+    return hyps, scores.gather(1, order)
 
 
 # ---------------------------------------------------------------------------

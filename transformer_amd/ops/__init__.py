@@ -58,6 +58,10 @@ from .functional import (  # noqa: E402
     linear_rows,
     linear_rows_residual_layernorm,
     linear_rows_workspace,
+    beam_search_workspace,
+    beam_topk,
+    beam_gather_table,
+    beam_gather_kv,
     residual_layernorm,
     dropout_residual_layernorm,
     linear_dropout_residual_layernorm,

@@ -90,6 +90,19 @@ torch::Tensor linear_rows_ln(torch::Tensor x, torch::Tensor w,
                              int64_t nw);
 torch::Tensor linear_rows_workspace(int64_t M, int64_t N);
 
+std::vector<torch::Tensor> beam_topk(torch::Tensor logits,
+                                     torch::Tensor scores,
+                                     torch::Tensor finished,
+                                     torch::Tensor lens, int64_t end_id,
+                                     torch::Tensor ws, int64_t nchunk);
+torch::Tensor beam_search_workspace(int64_t B, int64_t K, int64_t V,
+                                    int64_t nchunk);
+torch::Tensor beam_gather_table(std::vector<torch::Tensor> src,
+                                std::vector<torch::Tensor> dst);
+void beam_gather_kv(std::vector<torch::Tensor> src,
+                    std::vector<torch::Tensor> dst, torch::Tensor table,
+                    torch::Tensor src_row, torch::Tensor kv_len);
+
 torch::Tensor embed_pe_fwd(torch::Tensor tokens, torch::Tensor weight,
                            torch::Tensor pe,
                            c10::optional<torch::Tensor> positions);
@@ -284,6 +297,32 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "zeroed ticket + fp32 (M,N) pre-norm rows for linear_rows_ln; "
         "allocate once outside graph capture, share per stream only",
         pybind11::arg("M"), pybind11::arg("N"));
+  m.def("beam_topk", &beam_topk,
+        "beam-search candidate selection in one launch: per sentence the K "
+        "best of K*V by scores[b,k] + log_softmax(logits[b,k])[v], ties to "
+        "the lower k*V+v; returns [next_tok (B*K,1) int64, parent (B,K), "
+        "src_row (B*K,), scores, finished, lens].  A finished row offers "
+        "(token 0, score unchanged), a -inf row nothing; neither's logits "
+        "are read.  nchunk 0 = host rule, else forced (tests, sweeps)",
+        pybind11::arg("logits"), pybind11::arg("scores"),
+        pybind11::arg("finished"), pybind11::arg("lens"),
+        pybind11::arg("end_id"), pybind11::arg("ws"),
+        pybind11::arg("nchunk") = 0);
+  m.def("beam_search_workspace", &beam_search_workspace,
+        "zeroed tickets + per-chunk records for beam_topk; allocate once "
+        "outside graph capture, share per stream only",
+        pybind11::arg("B"), pybind11::arg("K"), pybind11::arg("V"),
+        pybind11::arg("nchunk") = 0);
+  m.def("beam_gather_table", &beam_gather_table,
+        "device table of layer base pointers for beam_gather_kv(src, dst); "
+        "build once outside graph capture",
+        pybind11::arg("src"), pybind11::arg("dst"));
+  m.def("beam_gather_kv", &beam_gather_kv,
+        "dst[l][r,:n] = src[l][src_row[r],:n], n = kv_len[src_row[r]]+1 "
+        "(<= Lmax), all layers in one launch; src and dst are distinct "
+        "(rows,Lmax,2,H,dh) cache sets, positions >= n are not written",
+        pybind11::arg("src"), pybind11::arg("dst"), pybind11::arg("table"),
+        pybind11::arg("src_row"), pybind11::arg("kv_len"));
   m.def("embed_pe_fwd", &embed_pe_fwd, pybind11::arg("tokens"),
         pybind11::arg("weight"), pybind11::arg("pe"),
         pybind11::arg("positions") = pybind11::none());

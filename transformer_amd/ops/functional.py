@@ -725,6 +725,61 @@ def linear_rows_residual_layernorm(x, w, b, res, gamma, beta, eps, ws):
 
 
 # ---------------------------------------------------------------------------
+# Beam search (forward only, csrc/beam_search.hip): candidate selection and
+# the self-attention cache reorder, one launch each per decode step.
+# ---------------------------------------------------------------------------
+
+def beam_search_workspace(B, K, V, device=None, nchunk=0):
+    """Scratch for beam_topk over B sentences, K beams and V columns
+    (nchunk: as beam_topk's, for forced chunk counts).  Allocate it once,
+    outside graph capture; share it per stream only.  CPU: an empty
+    placeholder."""
+    dev = torch.device(device if device is not None else
+                       ("cuda" if torch.cuda.is_available() else "cpu"))
+    if dev.type != "cuda":
+        return torch.zeros(0)
+    with torch.cuda.device(dev):
+        return ext().beam_search_workspace(B, K, V, nchunk)
+
+
+def beam_topk(logits, scores, finished, lens, end_id, ws, nchunk=0):
+    """One beam-search selection step.  logits (B*K,V) or (B*K,1,V) bf16;
+    scores (B,K) fp32 cumulative log-probs (-inf = dead beam); finished
+    (B,K) uint8; lens (B,K) int32; ws: beam_search_workspace.  1 <= K <= 8.
+    Returns (next_tok (B*K,1) int64, parent (B,K) int32, src_row (B*K,)
+    int32, scores, finished, lens), best first per sentence; semantics in
+    reference.beam_topk.  nchunk 0 = the host rule (about 2048 columns per
+    block), else a forced chunk count."""
+    if logits.is_cuda:
+        return tuple(ext().beam_topk(
+            logits.reshape(-1, logits.shape[-1]), scores, finished, lens,
+            end_id, ws, nchunk))
+    return R.beam_topk(logits, scores, finished, lens, end_id)
+
+
+def beam_gather_table(src, dst):
+    """The device table of layer base pointers beam_gather_kv(src, dst)
+    reads; build it once per direction, outside graph capture, and keep the
+    caches alive as long as it.  CPU: None."""
+    if not src[0].is_cuda:
+        return None
+    return ext().beam_gather_table(list(src), list(dst))
+
+
+def beam_gather_kv(src, dst, src_row, kv_len, table=None):
+    """dst[l][r, :n] = src[l][src_row[r], :n], n = kv_len[src_row[r]] + 1
+    (at most Lmax), for all layers in one launch.  src, dst: lists of
+    (rows,Lmax,2,H,dh) caches, two distinct sets (never in place; the caller
+    swaps them afterwards).  Positions >= n of dst are not written.  table:
+    beam_gather_table(src, dst); built here when omitted."""
+    if not src[0].is_cuda:
+        return R.beam_gather_kv(src, dst, src_row, kv_len)
+    if table is None:
+        table = beam_gather_table(src, dst)
+    ext().beam_gather_kv(list(src), list(dst), table, src_row, kv_len)
+
+
+# ---------------------------------------------------------------------------
 # Fused embedding * sqrt(d) + positional encoding (K10).
 # ---------------------------------------------------------------------------
 

@@ -131,6 +131,60 @@ def decode_attention_cross(q, kv, kv_pad=None):
 
 
 # ---------------------------------------------------------------------------
+# Beam search (csrc/beam_search.hip): candidate selection and cache reorder.
+# ---------------------------------------------------------------------------
+
+def beam_topk(logits, scores, finished, lens, end_id):
+    """logits (B*K,V); scores (B,K) fp32 cumulative log-probs, -inf = dead
+    beam; finished (B,K) uint8; lens (B,K) int32.  Per sentence the K best
+    of K*V by scores + log_softmax(logits), best first, equal scores to the
+    lower flat index k*V + v (stable sort).  A finished beam offers one
+    candidate (token 0, score and length unchanged), a dead beam none; a
+    sentence with fewer than K candidates pads with dead, finished slots.
+    Returns (next_tok (B*K,1) int64, parent (B,K) int32, src_row (B*K,)
+    int32, scores, finished, lens)."""
+    B, K = scores.shape
+    V = logits.shape[-1]
+    ninf = float("-inf")
+    scores = scores.float()
+    fin = finished.bool()
+    cand = scores[:, :, None] + torch.log_softmax(
+        logits.reshape(B, K, V).float(), dim=-1)
+    keep = torch.full_like(cand, ninf)
+    keep[:, :, 0] = scores
+    dead = (scores == ninf)[:, :, None]
+    cand = torch.where(fin[:, :, None], keep, cand)
+    cand = torch.where(dead, torch.full_like(cand, ninf), cand)
+    val, idx = torch.sort(cand.reshape(B, K * V), dim=1, descending=True,
+                          stable=True)
+    val, idx = val[:, :K], idx[:, :K]
+    empty = val == ninf
+    slot = torch.arange(K, device=scores.device).expand(B, K)
+    parent = torch.where(empty, slot, idx // V)
+    tok = torch.where(empty, torch.zeros_like(idx), idx % V)
+    pfin = fin.gather(1, parent)
+    plen = lens.gather(1, parent)
+    new_fin = pfin | (tok == end_id) | empty
+    new_len = plen + (~pfin & ~empty).to(lens.dtype)
+    src_row = (torch.arange(B, device=scores.device)[:, None] * K
+               + parent).reshape(-1)
+    return (tok.reshape(B * K, 1), parent.to(torch.int32),
+            src_row.to(torch.int32), val, new_fin.to(torch.uint8), new_len)
+
+
+def beam_gather_kv(src, dst, src_row, kv_len):
+    """dst[l][r, :n] = src[l][src_row[r], :n] for every layer l and row r,
+    n = kv_len[src_row[r]] + 1 clamped to Lmax (the +1 is the position the
+    step appended).  src and dst are lists of distinct (rows,Lmax,2,H,dh)
+    caches; positions >= n of dst keep their contents."""
+    Lmax = src[0].shape[1]
+    for r, sr in enumerate(src_row.tolist()):
+        n = min(max(int(kv_len[sr]), 0), Lmax - 1) + 1
+        for s, d in zip(src, dst):
+            d[r, :n] = s[sr, :n]
+
+
+# ---------------------------------------------------------------------------
 # K9 — fused residual-add + LayerNorm (post-LN residual, eps=1e-6;
 # reference Encoder.py:13-14,23,27).
 # ---------------------------------------------------------------------------
