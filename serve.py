@@ -5,7 +5,7 @@ serving side of that capability).
     python serve.py --model_dir model --src_vocab src_vocab.txt \
         --tgt_vocab tgt_vocab.txt [--device cuda] [--port 8000] \
         [--fused_decode_attn] [--skinny_decode_linear [--skinny_decode_ln]] \
-        [--beam_size N [--length_penalty A]]
+        [--beam_size N [--length_penalty A] [--beam_indirect_kv]]
 
 Endpoints:
     GET  /health               -> {"status": "ok", "config": {...}}
@@ -42,7 +42,7 @@ def build_app(model_dir: str, src_vocab: str, tgt_vocab: str,
               fused_decode_attn: bool = False,
               skinny_decode_linear: bool = False,
               skinny_decode_ln: bool = False, beam_size: int = 1,
-              length_penalty: float = 0.0):
+              length_penalty: float = 0.0, beam_indirect_kv: bool = False):
     from fastapi import Body, FastAPI
 
     from transformer_amd.runtime.export import load_exported
@@ -114,7 +114,8 @@ def build_app(model_dir: str, src_vocab: str, tgt_vocab: str,
                         model, enc_in, tgt_start, tgt_start + 1,
                         beam_size=beams, max_len=max_len,
                         length_penalty=length_penalty,
-                        skinny_linear=skinny_decode_linear)
+                        skinny_linear=skinny_decode_linear,
+                        indirect_kv=beam_indirect_kv)
                 out, score = hyps[:, 0], float(scores[0, 0])
             elif use_graph:
                 with graph_lock:
@@ -165,6 +166,11 @@ def parse_args(argv=None):
                         "overrides it; clamped to [1, 8]); 1 = greedy")
     p.add_argument("--length_penalty", type=float, default=0.0,
                    help="beam search ranks by score / ((5+len)/6)**this")
+    p.add_argument("--beam_indirect_kv", action="store_true",
+                   help="beam search without cache copies: self-attention "
+                        "reads the one cache set through origin tables, the "
+                        "beams of a sentence share its cross K/V (off by "
+                        "default)")
     return p.parse_args(argv)
 
 
@@ -179,7 +185,8 @@ def main(argv=None):
                     skinny_decode_linear=args.skinny_decode_linear,
                     skinny_decode_ln=args.skinny_decode_ln,
                     beam_size=args.beam_size,
-                    length_penalty=args.length_penalty)
+                    length_penalty=args.length_penalty,
+                    beam_indirect_kv=args.beam_indirect_kv)
     uvicorn.run(app, host=args.host, port=args.port)
 
 

@@ -339,7 +339,8 @@ class DecodeCache:
     def __init__(self, model: "Transformer", B: int, max_len: int,
                  enc_output: torch.Tensor, src_pad: torch.Tensor,
                  fused_attn: bool = False, skinny_linear: bool = False,
-                 skinny_ln: bool = False, second_kv: bool = False):
+                 skinny_ln: bool = False, second_kv: bool = False,
+                 beam_size: int = 1, indirect_kv: bool = False):
         dec = model.decoder
         d = dec.d_model
         layer0 = dec.layers[0]
@@ -365,11 +366,28 @@ class DecodeCache:
         Sk = enc_output.shape[1]
         for layer in dec.layers:
             kv = ops.linear(enc_output, layer.mha2.w_kv, layer.mha2.b_kv)
-            self.cross_kv.append(kv.view(B, Sk, 2, H, dh))
+            self.cross_kv.append(kv.view(enc_output.shape[0], Sk, 2, H, dh))
         # fused_attn: the decode-attention kernels track the row lengths on
         # the device and share one workspace across the layers
         self.kv_len = self.ws = None
-        if fused_attn:
+        # indirect_kv (beam search, B = sentences * beam_size rows): ONE
+        # self-attention cache set read through an origin table (uint8
+        # (B, Lt): which beam slot's physical row holds each cached position
+        # of a row), a second table the reorder writes INTO, and enc_output /
+        # src_pad with one row per SENTENCE, shared by the sentence's beams
+        self.beam_size = int(beam_size)
+        self.origin = self.origin_alt = None
+        if indirect_kv:
+            assert B % self.beam_size == 0 and not second_kv
+            assert enc_output.shape[0] * self.beam_size == B
+            Lt = (max_len + 15) // 16 * 16
+            self.origin = torch.zeros(B, Lt, dtype=torch.uint8, device=dev)
+            self.origin_alt = torch.zeros_like(self.origin)
+            self.kv_len = torch.zeros(B, dtype=torch.int32, device=dev)
+            self.ws = ops.decode_attention_beam_workspace(
+                B // self.beam_size, self.beam_size, H, dh, max(max_len, Sk),
+                dev)
+        elif fused_attn:
             self.kv_len = torch.zeros(B, dtype=torch.int32, device=dev)
             self.ws = ops.decode_attention_workspace(B, H, dh,
                                                      max(max_len, Sk), dev)
@@ -423,7 +441,11 @@ def decode_step(model, tokens_new, cache: DecodeCache):
         # new row, append k/v in place, attend over positions [0, t].
         qkv = lin(x, layer.mha1.w_qkv, layer.mha1.b_qkv)
         qkv = qkv.view(B, 1, 3, H, dh)
-        if cache.kv_len is not None:
+        if cache.origin is not None:
+            attn1 = ops.decode_attention_self_beam(
+                qkv, cache.self_kv[li], cache.kv_len, cache.origin,
+                cache.beam_size, cache.ws)
+        elif cache.kv_len is not None:
             attn1 = ops.decode_attention_self(qkv, cache.self_kv[li],
                                               cache.kv_len, cache.ws)
         else:
@@ -437,7 +459,11 @@ def decode_step(model, tokens_new, cache: DecodeCache):
         # cross-attention against precomputed encoder K/V
         q2 = lin(out1, layer.mha2.w_q, layer.mha2.b_q)
         q2 = q2.view(B, 1, H, dh)
-        if cache.kv_len is not None:
+        if cache.origin is not None:
+            attn2 = ops.decode_attention_cross_beam(
+                q2, cache.cross_kv[li], cache.src_pad, cache.beam_size,
+                cache.ws)
+        elif cache.kv_len is not None:
             attn2 = ops.decode_attention_cross(q2, cache.cross_kv[li],
                                                cache.src_pad, cache.ws)
         else:
@@ -496,7 +522,8 @@ def mask_after_end(out: torch.Tensor, end_id: int) -> torch.Tensor:
 
 @torch.no_grad()
 def beam_search_decode(model, inp, start_id, end_id, beam_size=4, max_len=10,
-                       length_penalty=0.0, skinny_linear=False):
+                       length_penalty=0.0, skinny_linear=False,
+                       indirect_kv=False):
     """KV-cached beam search.  inp (B, S) int64.  Returns (hyps, scores):
     hyps (B, K, <=max_len+1) int64 starting with start_id, tokens after the
     first end_id zeroed; scores (B, K) fp32 cumulative log-probs; both
@@ -507,15 +534,29 @@ def beam_search_decode(model, inp, start_id, end_id, beam_size=4, max_len=10,
     history to its new row, from one set into the other), swap the sets.
     A finished hypothesis keeps its slot and its score and is fed token 0;
     all per-step state stays on the device, and the host reads one flag per
-    step to stop when every beam is finished."""
+    step to stop when every beam is finished.
+
+    indirect_kv: no cache row ever moves.  One cache set; self-attention
+    reads each past key from whichever row of the sentence holds it, through
+    an origin table (ops.decode_attention_self_beam); the per-step reorder
+    is ops.beam_reindex on the tables (t bytes per row) and a swap of the
+    two tables; the encoder output is not repeated, and the K beams of a
+    sentence share one pass over its cross K/V
+    (ops.decode_attention_cross_beam)."""
     K = int(beam_size)
     assert 1 <= K <= 8, "beam_size must be in [1, 8]"
     B, dev = inp.shape[0], inp.device
     enc_output, src_pad = encode(model, inp)
-    cache = DecodeCache(model, B * K, max_len + 1,
-                        enc_output.repeat_interleave(K, dim=0),
-                        src_pad.repeat_interleave(K, dim=0), fused_attn=True,
-                        skinny_linear=skinny_linear, second_kv=True)
+    if indirect_kv:
+        cache = DecodeCache(model, B * K, max_len + 1, enc_output, src_pad,
+                            fused_attn=True, skinny_linear=skinny_linear,
+                            beam_size=K, indirect_kv=True)
+    else:
+        cache = DecodeCache(model, B * K, max_len + 1,
+                            enc_output.repeat_interleave(K, dim=0),
+                            src_pad.repeat_interleave(K, dim=0),
+                            fused_attn=True, skinny_linear=skinny_linear,
+                            second_kv=True)
     ws = ops.beam_search_workspace(B, K, model.w_final.shape[0], dev)
     scores = torch.full((B, K), float("-inf"), device=dev)
     scores[:, 0] = 0.0                      # one live beam per sentence
@@ -532,9 +573,15 @@ def beam_search_decode(model, inp, start_id, end_id, beam_size=4, max_len=10,
         logits = decode_step(model, tok, cache)
         tok, parent, src_row, scores, finished, lens = ops.beam_topk(
             logits, scores, finished, lens, end_id, ws)
-        ops.beam_gather_kv(cache.self_kv, cache.self_kv_alt, src_row,
-                           kv_before, cache.gather_tables[t % 2])
-        cache.self_kv, cache.self_kv_alt = cache.self_kv_alt, cache.self_kv
+        if indirect_kv:
+            ops.beam_reindex(cache.origin, cache.origin_alt, src_row,
+                             kv_before, K, max_len + 1)
+            cache.origin, cache.origin_alt = cache.origin_alt, cache.origin
+        else:
+            ops.beam_gather_kv(cache.self_kv, cache.self_kv_alt, src_row,
+                               kv_before, cache.gather_tables[t % 2])
+            cache.self_kv, cache.self_kv_alt = (cache.self_kv_alt,
+                                                cache.self_kv)
         kv_before.add_(1)
         tok_hist[t] = tok.view(B, K)
         par_hist[t] = parent

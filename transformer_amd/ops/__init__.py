@@ -62,6 +62,10 @@ from .functional import (  # noqa: E402
     beam_topk,
     beam_gather_table,
     beam_gather_kv,
+    beam_reindex,
+    decode_attention_self_beam,
+    decode_attention_cross_beam,
+    decode_attention_beam_workspace,
     residual_layernorm,
     dropout_residual_layernorm,
     linear_dropout_residual_layernorm,

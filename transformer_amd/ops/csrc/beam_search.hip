@@ -300,6 +300,37 @@ void beam_gather_kv_kernel(const long* __restrict__ table,
   }
 }
 
+// The reorder when self-attention reads through an origin table
+// (decode_attn.hip, BEAM): out[r, :n] = in[src_row[r], :n], n =
+// kv_before[src_row[r]] clamped to [0, Lmax], and, unless the row is full,
+// out[r, n] = src_row[r] % K: the position the step just appended sits in
+// the parent's physical row.  One byte per cached position: the span of a
+// row is a flat 16-byte stream with a byte tail.  grid = (span chunk, row),
+// 4 KiB of table per block; the block that owns byte n writes the entry.
+// Bytes past the written span are not touched.
+__global__ __launch_bounds__(BS_THREADS)
+void beam_reindex_kernel(const unsigned char* __restrict__ in,
+                         unsigned char* __restrict__ out,
+                         const int* __restrict__ src_row,
+                         const int* __restrict__ kv_before, int rows, int K,
+                         int Lmax, int Lt) {
+  const int r = blockIdx.y, tid = threadIdx.x;
+  const int sr = src_row[r];
+  if (sr < 0 || sr >= rows) return;
+  const int n = min(max(kv_before[sr], 0), Lmax);
+  const int c0 = blockIdx.x * (BS_THREADS * 16);   // this block's first byte
+  if (c0 > n) return;
+  const unsigned char* s = in + (long)sr * Lt;
+  unsigned char* d = out + (long)r * Lt;
+  const int p = c0 + tid * 16;
+  if (p + 16 <= n) {
+    *(i32x4*)(d + p) = *(const i32x4*)(s + p);
+  } else {
+    for (int i = p; i < n; ++i) d[i] = s[i];       // the tail: < 16 bytes
+  }
+  if (n < Lmax && n >= p && n < p + 16) d[n] = (unsigned char)(sr % K);
+}
+
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma clang attribute pop
 #endif
@@ -467,4 +498,38 @@ void beam_gather_kv(std::vector<torch::Tensor> src,
       (const long*)table.data_ptr<int64_t>(), src_row.data_ptr<int>(),
       kv_len.data_ptr<int>(), (int)rows, (int)Lmax, pos_vecs, row_vecs,
       (int)NL);
+}
+
+void beam_reindex(torch::Tensor origin_in, torch::Tensor origin_out,
+                  torch::Tensor src_row, torch::Tensor kv_before, int64_t K,
+                  int64_t Lmax) {
+  TORCH_CHECK(K >= 1 && K <= BS_MAX_K, "beam_reindex: need 1 <= K <= ",
+              BS_MAX_K);
+  for (const auto* t : {&origin_in, &origin_out})
+    TORCH_CHECK(t->is_cuda() && t->dtype() == torch::kUInt8 && t->dim() == 2 &&
+                t->is_contiguous() && t->sizes() == origin_in.sizes() &&
+                t->size(1) % 16 == 0 && (uintptr_t)t->data_ptr() % 16 == 0,
+                "beam_reindex: tables must be contiguous, 16-byte-aligned "
+                "uint8 (rows,Lt) GPU tensors of one shape, Lt % 16 == 0");
+  const int64_t rows = origin_in.size(0), Lt = origin_in.size(1);
+  const uintptr_t pi = (uintptr_t)origin_in.data_ptr();
+  const uintptr_t po = (uintptr_t)origin_out.data_ptr();
+  const uintptr_t bytes = (uintptr_t)(rows * Lt);
+  TORCH_CHECK(pi + bytes <= po || po + bytes <= pi,
+              "beam_reindex: origin_in and origin_out must be distinct tables "
+              "(the reorder is never in place)");
+  TORCH_CHECK(Lmax >= 1 && Lmax <= Lt && rows % K == 0 && rows <= 65535,
+              "beam_reindex: need 1 <= Lmax <= Lt and rows = B*K <= 65535");
+  for (const auto* t : {&src_row, &kv_before})
+    TORCH_CHECK(t->is_cuda() && t->dtype() == torch::kInt32 &&
+                t->is_contiguous() && t->dim() == 1 && t->size(0) == rows,
+                "beam_reindex: src_row and kv_before must be contiguous int32 "
+                "(rows,) GPU tensors");
+  if (rows == 0) return;
+  const unsigned gx = (unsigned)cdiv((int)Lmax, BS_THREADS * 16);
+  auto stream = at::hip::getCurrentHIPStream();
+  beam_reindex_kernel<<<dim3(gx, (unsigned)rows), BS_THREADS, 0, stream>>>(
+      origin_in.data_ptr<unsigned char>(),
+      origin_out.data_ptr<unsigned char>(), src_row.data_ptr<int>(),
+      kv_before.data_ptr<int>(), (int)rows, (int)K, (int)Lmax, (int)Lt);
 }

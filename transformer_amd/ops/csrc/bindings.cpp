@@ -79,6 +79,19 @@ torch::Tensor decode_attn_cross(torch::Tensor q, torch::Tensor kv,
 torch::Tensor decode_attn_workspace(int64_t B, int64_t H, int64_t dh,
                                     int64_t L);
 int64_t decode_attn_nsplit(int64_t BH, int64_t L);
+torch::Tensor decode_attn_self_beam(torch::Tensor qkv, torch::Tensor kv_cache,
+                                    torch::Tensor kv_len, torch::Tensor origin,
+                                    int64_t K, torch::Tensor ws, double scale,
+                                    int64_t nsplit);
+torch::Tensor decode_attn_cross_beam(torch::Tensor q, torch::Tensor kv,
+                                     torch::Tensor kv_pad, int64_t K,
+                                     torch::Tensor ws, double scale,
+                                     int64_t nsplit);
+torch::Tensor decode_attn_beam_workspace(int64_t B, int64_t K, int64_t H,
+                                         int64_t dh, int64_t L);
+void beam_reindex(torch::Tensor origin_in, torch::Tensor origin_out,
+                  torch::Tensor src_row, torch::Tensor kv_before, int64_t K,
+                  int64_t Lmax);
 
 torch::Tensor linear_rows(torch::Tensor x, torch::Tensor w,
                           c10::optional<torch::Tensor> bias, bool relu,
@@ -323,6 +336,36 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(rows,Lmax,2,H,dh) cache sets, positions >= n are not written",
         pybind11::arg("src"), pybind11::arg("dst"), pybind11::arg("table"),
         pybind11::arg("src_row"), pybind11::arg("kv_len"));
+  m.def("beam_reindex", &beam_reindex,
+        "origin_out[r,:n] = origin_in[src_row[r],:n], n = "
+        "kv_before[src_row[r]] clamped to [0,Lmax], and origin_out[r,n] = "
+        "src_row[r] % K unless n == Lmax; distinct uint8 (B*K,Lt) tables, "
+        "bytes past the written span are not touched",
+        pybind11::arg("origin_in"), pybind11::arg("origin_out"),
+        pybind11::arg("src_row"), pybind11::arg("kv_before"),
+        pybind11::arg("K"), pybind11::arg("Lmax"));
+  m.def("decode_attn_self_beam", &decode_attn_self_beam,
+        "decode_attn_self for B*K beam rows, K per sentence: cached key j of "
+        "row r is read from row (r/K)*K + min(origin[r,j], K-1); the new key "
+        "and the append are the row's own.  The K rows of a sentence must "
+        "have equal kv_len.  origin: uint8 (B*K,Lt), Lt >= Lmax, Lt % 16 == 0",
+        pybind11::arg("qkv"), pybind11::arg("kv_cache"),
+        pybind11::arg("kv_len"), pybind11::arg("origin"), pybind11::arg("K"),
+        pybind11::arg("ws"), pybind11::arg("scale"),
+        pybind11::arg("nsplit") = 0);
+  m.def("decode_attn_cross_beam", &decode_attn_cross_beam,
+        "cross-attention of q (B*K,1,H,dh) over un-replicated (B,Sk,2,H,dh) "
+        "K/V: the K queries of a sentence share one pass over its keys; "
+        "kv_pad (B,Sk).  K = 1 runs decode_attn_cross",
+        pybind11::arg("q"), pybind11::arg("kv"), pybind11::arg("kv_pad"),
+        pybind11::arg("K"), pybind11::arg("ws"), pybind11::arg("scale"),
+        pybind11::arg("nsplit") = 0);
+  m.def("decode_attn_beam_workspace", &decode_attn_beam_workspace,
+        "zeroed tickets + fp32 partials shared by decode_attn_self_beam and "
+        "decode_attn_cross_beam for key windows up to L; allocate once "
+        "outside graph capture, share per stream only",
+        pybind11::arg("B"), pybind11::arg("K"), pybind11::arg("H"),
+        pybind11::arg("dh"), pybind11::arg("L"));
   m.def("embed_pe_fwd", &embed_pe_fwd, pybind11::arg("tokens"),
         pybind11::arg("weight"), pybind11::arg("pe"),
         pybind11::arg("positions") = pybind11::none());

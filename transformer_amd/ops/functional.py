@@ -436,6 +436,45 @@ def decode_attention_cross(q, kv, kv_pad, ws):
     return R.decode_attention_cross(q, kv, kv_pad)
 
 
+def decode_attention_beam_workspace(B, K, H, dh, L, device=None):
+    """Scratch shared by decode_attention_self_beam and _cross_beam for B
+    sentences of K beams and key windows up to L; the rules of
+    decode_attention_workspace apply.  CPU: an empty placeholder."""
+    dev = torch.device(device if device is not None else
+                       ("cuda" if torch.cuda.is_available() else "cpu"))
+    if dev.type != "cuda":
+        return torch.zeros(0)
+    with torch.cuda.device(dev):
+        return ext().decode_attn_beam_workspace(B, K, H, dh, L)
+
+
+def decode_attention_self_beam(qkv, kv_cache, kv_len, origin, K, ws):
+    """decode_attention_self for the B*K rows of a beam search (row r is beam
+    r % K of sentence r // K) without moving the cache: origin (B*K,Lt)
+    uint8, Lt >= Lmax, Lt % 16 == 0, names for each cached position j <
+    kv_len[r] the beam slot whose physical row holds row r's key j, which is
+    read from kv_cache[(r // K) * K + min(origin[r, j], K - 1), j].  The new
+    key is read from qkv[r] and stored to kv_cache[r, kv_len[r]], the row's
+    own slot (nothing once full); entries at j >= kv_len[r] are never read.
+    PRECONDITION, not checked (the lengths live on the device): the K rows
+    of a sentence have equal kv_len, so no row reads a slot that another
+    row of the launch writes."""
+    if qkv.is_cuda:
+        return ext().decode_attn_self_beam(qkv, kv_cache, kv_len, origin, K,
+                                           ws, 1.0 / math.sqrt(qkv.shape[-1]))
+    return R.decode_attention_self_beam(qkv, kv_cache, kv_len, origin, K)
+
+
+def decode_attention_cross_beam(q, kv, kv_pad, K, ws):
+    """q (B*K,1,H,dh), possibly a strided view; kv (B,Sk,2,H,dh) and kv_pad
+    (B,Sk) uint8 or None, one copy per SENTENCE: the K queries of a sentence
+    share one pass over its keys.  Returns (B*K,1,H,dh)."""
+    if q.is_cuda:
+        return ext().decode_attn_cross_beam(q, kv, _opt(kv_pad), K, ws,
+                                            1.0 / math.sqrt(q.shape[-1]))
+    return R.decode_attention_cross_beam(q, kv, kv_pad, K)
+
+
 # ---------------------------------------------------------------------------
 # Fused (dropout +) residual-add + LayerNorm, eps=1e-6 (K9), alone and as
 # the tail of the sublayer composites: LN(dropout(linear(x)) + res) and the
@@ -777,6 +816,24 @@ def beam_gather_kv(src, dst, src_row, kv_len, table=None):
     if table is None:
         table = beam_gather_table(src, dst)
     ext().beam_gather_kv(list(src), list(dst), table, src_row, kv_len)
+
+
+def beam_reindex(origin_in, origin_out, src_row, kv_before, K, Lmax=None):
+    """The reorder of a beam search whose self-attention reads through origin
+    tables (decode_attention_self_beam): origin_out[r, :n] =
+    origin_in[src_row[r], :n] with n = kv_before[src_row[r]] clamped to
+    [0, Lmax], and origin_out[r, n] = src_row[r] % K unless n == Lmax (the
+    position the step appended sits in the parent's row).  Two distinct
+    (B*K,Lt) uint8 tables (the caller swaps them); bytes past the written
+    span keep their contents.  Lmax: the cache length, default Lt."""
+    if origin_in.data_ptr() == origin_out.data_ptr():
+        raise RuntimeError("beam_reindex: origin_in and origin_out must be "
+                           "distinct tables (the reorder is never in place)")
+    if not origin_in.is_cuda:
+        return R.beam_reindex(origin_in, origin_out, src_row, kv_before, K,
+                              Lmax)
+    ext().beam_reindex(origin_in, origin_out, src_row, kv_before, K,
+                       origin_in.shape[1] if Lmax is None else Lmax)
 
 
 # ---------------------------------------------------------------------------

@@ -184,6 +184,42 @@ def beam_gather_kv(src, dst, src_row, kv_len):
             d[r, :n] = s[sr, :n]
 
 
+def beam_reindex(origin_in, origin_out, src_row, kv_before, K, Lmax=None):
+    """origin_out[r, :n] = origin_in[src_row[r], :n], n = kv_before[src_row[r]]
+    clamped to [0, Lmax]; unless n == Lmax, origin_out[r, n] = src_row[r] % K
+    (the position the step appended sits in the parent's row).  Bytes past
+    the written span keep their contents.  Lmax defaults to the table width."""
+    Lmax = origin_in.shape[1] if Lmax is None else Lmax
+    for r, sr in enumerate(src_row.tolist()):
+        n = min(max(int(kv_before[sr]), 0), Lmax)
+        origin_out[r, :n] = origin_in[sr, :n]
+        if n < Lmax:
+            origin_out[r, n] = sr % K
+
+
+def decode_attention_self_beam(qkv, kv_cache, kv_len, origin, K):
+    """decode_attention_self over the cache gathered through the table: key
+    j < kv_len[r] of row r comes from row (r//K)*K + min(origin[r, j], K-1).
+    The append goes to kv_cache[r, kv_len[r]], the row's own slot."""
+    R, Lmax = kv_cache.shape[:2]
+    rows = torch.arange(R, device=kv_cache.device)
+    src = (rows // K * K)[:, None] + origin[:, :Lmax].long().clamp(max=K - 1)
+    pos = torch.arange(Lmax, device=kv_cache.device).expand(R, Lmax)
+    gathered = kv_cache[src, pos]
+    out = decode_attention_self(qkv, gathered, kv_len)
+    n = kv_len.long().clamp(0, Lmax)
+    live = n < Lmax
+    kv_cache[rows[live], n[live]] = qkv[live, 0, 1:3]
+    return out
+
+
+def decode_attention_cross_beam(q, kv, kv_pad, K):
+    """decode_attention_cross of q (B*K,1,H,dh) over kv (B,Sk,2,H,dh) and
+    kv_pad (B,Sk): row r attends sentence r // K."""
+    pad = None if kv_pad is None else kv_pad.repeat_interleave(K, dim=0)
+    return decode_attention_cross(q, kv.repeat_interleave(K, dim=0), pad)
+
+
 # ---------------------------------------------------------------------------
 # K9 — fused residual-add + LayerNorm (post-LN residual, eps=1e-6;
 # reference Encoder.py:13-14,23,27).
