@@ -4,7 +4,8 @@ serving side of that capability).
 
     python serve.py --model_dir model --src_vocab src_vocab.txt \
         --tgt_vocab tgt_vocab.txt [--device cuda] [--port 8000] \
-        [--fused_decode_attn] [--skinny_decode_linear [--skinny_decode_ln]] \
+        [--fused_decode_attn] [--skinny_decode_linear \
+            [--skinny_decode_ln | --skinny_decode_preln]] \
         [--beam_size N [--length_penalty A] [--beam_indirect_kv]]
 
 Endpoints:
@@ -42,7 +43,8 @@ def build_app(model_dir: str, src_vocab: str, tgt_vocab: str,
               fused_decode_attn: bool = False,
               skinny_decode_linear: bool = False,
               skinny_decode_ln: bool = False, beam_size: int = 1,
-              length_penalty: float = 0.0, beam_indirect_kv: bool = False):
+              length_penalty: float = 0.0, beam_indirect_kv: bool = False,
+              skinny_decode_preln: bool = False):
     from fastapi import Body, FastAPI
 
     from transformer_amd.runtime.export import load_exported
@@ -84,7 +86,8 @@ def build_app(model_dir: str, src_vocab: str, tgt_vocab: str,
                 device=next(model.parameters()).device,
                 fused_attn=fused_decode_attn,
                 skinny_linear=skinny_decode_linear,
-                skinny_ln=skinny_decode_ln)
+                skinny_ln=skinny_decode_ln,
+                skinny_preln=skinny_decode_preln)
         return graphed[key], key[0]
 
     app = FastAPI(title="transformer_amd", version="1.0")
@@ -115,7 +118,8 @@ def build_app(model_dir: str, src_vocab: str, tgt_vocab: str,
                         beam_size=beams, max_len=max_len,
                         length_penalty=length_penalty,
                         skinny_linear=skinny_decode_linear,
-                        indirect_kv=beam_indirect_kv)
+                        indirect_kv=beam_indirect_kv,
+                        skinny_preln=skinny_decode_preln)
                 out, score = hyps[:, 0], float(scores[0, 0])
             elif use_graph:
                 with graph_lock:
@@ -129,7 +133,8 @@ def build_app(model_dir: str, src_vocab: str, tgt_vocab: str,
                                     max_len=max_len,
                                     fused_attn=fused_decode_attn,
                                     skinny_linear=skinny_decode_linear,
-                                    skinny_ln=skinny_decode_ln)
+                                    skinny_ln=skinny_decode_ln,
+                                    skinny_preln=skinny_decode_preln)
         ids = out.squeeze(0).tolist()
         body = [t for t in ids if 0 < t < tgt_tok.vocab_size]
         return {"tokens": ids, "text": tgt_tok.decode(body), "score": score}
@@ -161,6 +166,11 @@ def parse_args(argv=None):
                    help="with --skinny_decode_linear: run the linears that "
                         "feed a LayerNorm fused with it, one launch each "
                         "(measured slower than two launches; off by default)")
+    p.add_argument("--skinny_decode_preln", action="store_true",
+                   help="with --skinny_decode_linear, not with "
+                        "--skinny_decode_ln: run every LayerNorm of the step "
+                        "in the prologue of the linear that consumes it "
+                        "(off by default; docs/PERF.md)")
     p.add_argument("--beam_size", type=int, default=1,
                    help="default beams per request (a request's \"beam_size\" "
                         "overrides it; clamped to [1, 8]); 1 = greedy")
@@ -186,7 +196,8 @@ def main(argv=None):
                     skinny_decode_ln=args.skinny_decode_ln,
                     beam_size=args.beam_size,
                     length_penalty=args.length_penalty,
-                    beam_indirect_kv=args.beam_indirect_kv)
+                    beam_indirect_kv=args.beam_indirect_kv,
+                    skinny_decode_preln=args.skinny_decode_preln)
     uvicorn.run(app, host=args.host, port=args.port)
 
 

@@ -8,7 +8,9 @@ captured graph per token; with fused_attn=True each attention of the
 captured step is one split-KV launch that also appends the K/V row; with
 skinny_linear=True each linear of the step is one linear_rows launch, and
 with skinny_ln=True as well the three per layer that feed a LayerNorm run
-fused with it.
+fused with it; with skinny_preln=True instead, every LayerNorm of the step
+runs in the prologue of the linear that consumes it (compared with the
+skinny_linear column, its baseline).
 
     python tools/decode_bench.py [--reps N] [--long] [--no_eager]
 
@@ -80,12 +82,15 @@ for B, S, L in configs:
 
     decs = [GraphedDecoder(m, B=B, S_src=S, max_len=L, start_id=START,
                            device=torch.device("cuda"), fused_attn=f,
-                           skinny_linear=k, skinny_ln=n)
-            for f, k, n in ((False, False, False), (True, False, False),
-                            (True, True, False), (True, True, True))]
+                           skinny_linear=k, skinny_ln=n, skinny_preln=p)
+            for f, k, n, p in ((False, False, False, False),
+                               (True, False, False, False),
+                               (True, True, False, False),
+                               (True, True, True, False),
+                               (True, True, False, True))]
     for d in decs:
         d(inp, END, max_len=8)  # warm
-    ts, outs = ([], [], [], []), [None] * 4
+    ts, outs = ([], [], [], [], []), [None] * 5
     for _ in range(args.reps):
         for i, d in enumerate(decs):
             outs[i], t = timed(lambda: d(inp, END, max_len=L))
@@ -93,9 +98,10 @@ for B, S, L in configs:
     ok = same_until_end(outs[0], outs[1])
     ok_s = same_until_end(outs[0], outs[2])
     ok_n = same_until_end(outs[0], outs[3])
+    ok_p = same_until_end(outs[0], outs[4])
     if not args.no_eager:
         ok = ok and same_until_end(out_e, outs[0])
-    tg, tf, tk, tn = (statistics.median(t) for t in ts)
+    tg, tf, tk, tn, tp = (statistics.median(t) for t in ts)
     print(f"B={B} S={S} L={L}: {eager}graphed {stats(ts[0], L)} ms/tok "
           f"({B*L/tg:.0f} tok/s) | graphed+fused_attn {stats(ts[1], L)} "
           f"ms/tok ({B*L/tf:.0f} tok/s) | fused/graphed time {tf/tg:.3f} "
@@ -104,5 +110,8 @@ for B, S, L in configs:
           f"time {tk/tf:.3f} | tokens vs graphed "
           f"{'same' if ok_s else 'DIFFER'} | +skinny_ln "
           f"{stats(ts[3], L)} ms/tok | skinny_ln/skinny time {tn/tk:.3f} "
-          f"| tokens vs graphed {'same' if ok_n else 'DIFFER'}", flush=True)
+          f"| tokens vs graphed {'same' if ok_n else 'DIFFER'} | "
+          f"+skinny_preln {stats(ts[4], L)} ms/tok | skinny_preln/skinny "
+          f"time {tp/tk:.3f} | tokens vs graphed "
+          f"{'same' if ok_p else 'DIFFER'}", flush=True)
 print("decode bench done")

@@ -340,7 +340,9 @@ class DecodeCache:
                  enc_output: torch.Tensor, src_pad: torch.Tensor,
                  fused_attn: bool = False, skinny_linear: bool = False,
                  skinny_ln: bool = False, second_kv: bool = False,
-                 beam_size: int = 1, indirect_kv: bool = False):
+                 beam_size: int = 1, indirect_kv: bool = False,
+                 skinny_preln: bool = False):
+        _check_skinny(skinny_linear, skinny_ln, skinny_preln)
         dec = model.decoder
         d = dec.d_model
         layer0 = dec.layers[0]
@@ -393,8 +395,10 @@ class DecodeCache:
                                                      max(max_len, Sk), dev)
         # skinny_linear: the step's linears run ops.linear_rows; skinny_ln:
         # the three per layer that feed a LayerNorm run the fused variant
-        # and share one fp32 workspace
+        # and share one fp32 workspace; skinny_preln: every LayerNorm runs
+        # in the prologue of the linear that consumes it instead
         self.skinny_linear = skinny_linear
+        self.skinny_preln = skinny_preln
         self.lin_ws = (ops.linear_rows_workspace(B, d, dev)
                        if skinny_linear and skinny_ln else None)
 
@@ -404,6 +408,40 @@ def encode(model, inp, training=False):
     """Run the encoder once; returns (enc_output, src_pad)."""
     src_pad = (inp == 0).to(torch.uint8)
     return model.encoder(inp, src_pad, training), src_pad
+
+
+def _check_skinny(skinny_linear, skinny_ln, skinny_preln):
+    if skinny_preln and skinny_ln:
+        raise ValueError("skinny_preln and skinny_ln are mutually exclusive")
+    if skinny_preln and not skinny_linear:
+        raise ValueError("skinny_preln requires skinny_linear")
+
+
+def _preln_layers(model, x, self_attn, cross_attn):
+    """The decoder layers and the logits head of one step with every
+    LayerNorm folded into the linear that consumes its output
+    (ops.residual_layernorm_linear): ln1 into the cross w_q, ln2 into ffn.w1,
+    ln3 into the next layer's w_qkv or the head.  Layer 0's QKV takes the
+    embedding x and stays a plain linear.  self_attn(li, qkv) and
+    cross_attn(li, q2) are the caller's attentions, (B,1,d) out."""
+    lin, ln_lin = ops.linear_rows, ops.residual_layernorm_linear
+    layers = model.decoder.layers
+    qkv = lin(x, layers[0].mha1.w_qkv, layers[0].mha1.b_qkv)
+    for li, layer in enumerate(layers):
+        ln1, ln2, ln3, ffn = layer.ln1, layer.ln2, layer.ln3, layer.ffn
+        p1 = lin(self_attn(li, qkv), layer.mha1.w_o, layer.mha1.b_o)
+        out1, q2 = ln_lin(p1, x, ln1.gamma, ln1.beta, ln1.eps,
+                          layer.mha2.w_q, layer.mha2.b_q)
+        p2 = lin(cross_attn(li, q2), layer.mha2.w_o, layer.mha2.b_o)
+        out2, h = ln_lin(p2, out1, ln2.gamma, ln2.beta, ln2.eps, ffn.w1,
+                         ffn.b1, "relu")
+        p3 = lin(h, ffn.w2, ffn.b2)
+        if li + 1 < len(layers):
+            nw, nb = layers[li + 1].mha1.w_qkv, layers[li + 1].mha1.b_qkv
+        else:
+            nw, nb = model.w_final, model.b_final
+        x, qkv = ln_lin(p3, out2, ln3.gamma, ln3.beta, ln3.eps, nw, nb)
+    return qkv
 
 
 def _step_linears(skinny: bool, ln_ws=None):
@@ -435,11 +473,11 @@ def decode_step(model, tokens_new, cache: DecodeCache):
     lin, lin_ln = _step_linears(cache.skinny_linear, cache.lin_ws)
     # embedding * sqrt(d) + PE at position t
     x = ops.embedding_scale_pe_at(tokens_new, dec.embedding, dec.pe, t)
-    for li, layer in enumerate(dec.layers):
-        H, dh = layer.mha1.num_heads, layer.mha1.depth
-        # masked self-attention against the cache: project packed qkv for the
-        # new row, append k/v in place, attend over positions [0, t].
-        qkv = lin(x, layer.mha1.w_qkv, layer.mha1.b_qkv)
+    H, dh = dec.layers[0].mha1.num_heads, dec.layers[0].mha1.depth
+
+    def self_attn(li, qkv):
+        # masked self-attention against the cache: append the new row's k/v
+        # in place, attend over positions [0, t].
         qkv = qkv.view(B, 1, 3, H, dh)
         if cache.origin is not None:
             attn1 = ops.decode_attention_self_beam(
@@ -454,10 +492,10 @@ def decode_step(model, tokens_new, cache: DecodeCache):
             kv_hist = cache.self_kv[li][:, :t + 1]
             k, v = kv_hist.unbind(dim=2)
             attn1 = ops.fused_attention(q, k, v)  # all cached keys visible
-        out1 = lin_ln(attn1.reshape(B, 1, H * dh), layer.mha1.w_o,
-                      layer.mha1.b_o, x, layer.ln1)
+        return attn1.reshape(B, 1, H * dh)
+
+    def cross_attn(li, q2):
         # cross-attention against precomputed encoder K/V
-        q2 = lin(out1, layer.mha2.w_q, layer.mha2.b_q)
         q2 = q2.view(B, 1, H, dh)
         if cache.origin is not None:
             attn2 = ops.decode_attention_cross_beam(
@@ -469,20 +507,33 @@ def decode_step(model, tokens_new, cache: DecodeCache):
         else:
             k2, v2 = cache.cross_kv[li].unbind(dim=2)
             attn2 = ops.fused_attention(q2, k2, v2, kv_pad=cache.src_pad)
-        out2 = lin_ln(attn2.reshape(B, 1, H * dh), layer.mha2.w_o,
-                      layer.mha2.b_o, out1, layer.ln2)
-        ffn = layer.ffn
-        h = lin(out2, ffn.w1, ffn.b1, activation="relu")
-        x = lin_ln(h, ffn.w2, ffn.b2, out2, layer.ln3)
+        return attn2.reshape(B, 1, H * dh)
+
+    if cache.skinny_preln:
+        logits = _preln_layers(model, x, self_attn, cross_attn)
+    else:
+        for li, layer in enumerate(dec.layers):
+            # project packed qkv for the new row
+            qkv = lin(x, layer.mha1.w_qkv, layer.mha1.b_qkv)
+            out1 = lin_ln(self_attn(li, qkv), layer.mha1.w_o, layer.mha1.b_o,
+                          x, layer.ln1)
+            q2 = lin(out1, layer.mha2.w_q, layer.mha2.b_q)
+            out2 = lin_ln(cross_attn(li, q2), layer.mha2.w_o, layer.mha2.b_o,
+                          out1, layer.ln2)
+            ffn = layer.ffn
+            h = lin(out2, ffn.w1, ffn.b1, activation="relu")
+            x = lin_ln(h, ffn.w2, ffn.b2, out2, layer.ln3)
+        logits = lin(x, model.w_final, model.b_final)
     cache.pos = t + 1
     if cache.kv_len is not None:
         cache.kv_len.add_(1)
-    return lin(x, model.w_final, model.b_final)
+    return logits
 
 
 @torch.no_grad()
 def greedy_decode(model, inp, start_id, end_id, max_len=10,
-                  fused_attn=False, skinny_linear=False, skinny_ln=False):
+                  fused_attn=False, skinny_linear=False, skinny_ln=False,
+                  skinny_preln=False):
     """KV-cached greedy decode.  inp (B, S) int64; returns (B, <=max_len+1)
     token ids starting with start_id; stops early when every sequence has
     emitted end_id.  fused_attn: the single-query decode-attention kernels
@@ -490,12 +541,14 @@ def greedy_decode(model, inp, start_id, end_id, max_len=10,
     skinny_linear: the one-launch decode linear (ops.linear_rows) in place
     of the training GEMM; composes with fused_attn.  skinny_ln (with
     skinny_linear): the linears that feed a LayerNorm run fused with it
-    (ops.linear_rows_residual_layernorm)."""
+    (ops.linear_rows_residual_layernorm).  skinny_preln (with skinny_linear,
+    not with skinny_ln): every LayerNorm of the step runs in the prologue of
+    the linear that consumes it (ops.residual_layernorm_linear)."""
     B = inp.shape[0]
     enc_output, src_pad = encode(model, inp)
     cache = DecodeCache(model, B, max_len + 1, enc_output, src_pad,
                         fused_attn=fused_attn, skinny_linear=skinny_linear,
-                        skinny_ln=skinny_ln)
+                        skinny_ln=skinny_ln, skinny_preln=skinny_preln)
     out = torch.full((B, 1), start_id, dtype=torch.int64, device=inp.device)
     finished = torch.zeros(B, dtype=torch.bool, device=inp.device)
     for _ in range(max_len):
@@ -523,7 +576,7 @@ def mask_after_end(out: torch.Tensor, end_id: int) -> torch.Tensor:
 @torch.no_grad()
 def beam_search_decode(model, inp, start_id, end_id, beam_size=4, max_len=10,
                        length_penalty=0.0, skinny_linear=False,
-                       indirect_kv=False):
+                       indirect_kv=False, skinny_preln=False):
     """KV-cached beam search.  inp (B, S) int64.  Returns (hyps, scores):
     hyps (B, K, <=max_len+1) int64 starting with start_id, tokens after the
     first end_id zeroed; scores (B, K) fp32 cumulative log-probs; both
@@ -542,7 +595,9 @@ def beam_search_decode(model, inp, start_id, end_id, beam_size=4, max_len=10,
     is ops.beam_reindex on the tables (t bytes per row) and a swap of the
     two tables; the encoder output is not repeated, and the K beams of a
     sentence share one pass over its cross K/V
-    (ops.decode_attention_cross_beam)."""
+    (ops.decode_attention_cross_beam).
+
+    skinny_preln (with skinny_linear): as greedy_decode's."""
     K = int(beam_size)
     assert 1 <= K <= 8, "beam_size must be in [1, 8]"
     B, dev = inp.shape[0], inp.device
@@ -550,13 +605,14 @@ def beam_search_decode(model, inp, start_id, end_id, beam_size=4, max_len=10,
     if indirect_kv:
         cache = DecodeCache(model, B * K, max_len + 1, enc_output, src_pad,
                             fused_attn=True, skinny_linear=skinny_linear,
-                            beam_size=K, indirect_kv=True)
+                            beam_size=K, indirect_kv=True,
+                            skinny_preln=skinny_preln)
     else:
         cache = DecodeCache(model, B * K, max_len + 1,
                             enc_output.repeat_interleave(K, dim=0),
                             src_pad.repeat_interleave(K, dim=0),
                             fused_attn=True, skinny_linear=skinny_linear,
-                            second_kv=True)
+                            second_kv=True, skinny_preln=skinny_preln)
     ws = ops.beam_search_workspace(B, K, model.w_final.shape[0], dev)
     scores = torch.full((B, K), float("-inf"), device=dev)
     scores[:, 0] = 0.0                      # one live beam per sentence
@@ -619,7 +675,8 @@ class GraphedDecoder:
     @torch.no_grad()
     def __init__(self, model: "Transformer", B: int, S_src: int, max_len: int,
                  start_id: int, device, fused_attn: bool = False,
-                 skinny_linear: bool = False, skinny_ln: bool = False):
+                 skinny_linear: bool = False, skinny_ln: bool = False,
+                 skinny_preln: bool = False):
         """fused_attn: the captured step runs ops.decode_attention_self /
         _cross (append + attention in one launch each, over an int32 (B,)
         device length) in place of the pad-mask unmask, the cache
@@ -627,7 +684,11 @@ class GraphedDecoder:
         skinny_linear: every linear of the captured step is one
         ops.linear_rows launch (no split-K fill/finalize); skinny_ln
         (with skinny_linear): w_o, the cross w_o and ffn.w2 run fused with
-        the residual LayerNorm that follows them, one launch each."""
+        the residual LayerNorm that follows them, one launch each;
+        skinny_preln (with skinny_linear, not with skinny_ln): every
+        LayerNorm of the step runs in the prologue of the linear that
+        consumes it, so the step has no LayerNorm launch at all."""
+        _check_skinny(skinny_linear, skinny_ln, skinny_preln)
         assert max_len >= 4, "warmup+capture advance the position past 3"
         self.model = model
         self.B, self.S_src, self.max_len = B, S_src, max_len
@@ -674,8 +735,8 @@ class GraphedDecoder:
             pe_row = dec.pe.index_select(0, pos)           # (1,d) model dtype
             # same kernel as the eager decode path -> bit-identical tokens
             x = O.ext().embed_pe_fwd(cur, dec.embedding, pe_row)
-            for li, layer in enumerate(dec.layers):
-                qkv = lin(x, layer.mha1.w_qkv, layer.mha1.b_qkv)
+
+            def self_attn(li, qkv):
                 qkv = qkv.view(B, 1, 3, H, dh)
                 if fused_attn:
                     attn1 = O.decode_attention_self(qkv, self.self_kv[li],
@@ -685,9 +746,9 @@ class GraphedDecoder:
                     q = qkv[:, :, 0].contiguous()
                     k, v = self.self_kv[li].unbind(dim=2)
                     attn1 = O.fused_attention(q, k, v, kv_pad=self.kv_pad)
-                out1 = lin_ln(attn1.reshape(B, 1, H * dh), layer.mha1.w_o,
-                              layer.mha1.b_o, x, layer.ln1)
-                q2 = lin(out1, layer.mha2.w_q, layer.mha2.b_q)
+                return attn1.reshape(B, 1, H * dh)
+
+            def cross_attn(li, q2):
                 q2 = q2.view(B, 1, H, dh)
                 if fused_attn:
                     attn2 = O.decode_attention_cross(q2, self.cross_kv[li],
@@ -696,12 +757,22 @@ class GraphedDecoder:
                     k2, v2 = self.cross_kv[li].unbind(dim=2)
                     attn2 = O.fused_attention(q2, k2, v2,
                                               kv_pad=self.src_pad)
-                out2 = lin_ln(attn2.reshape(B, 1, H * dh), layer.mha2.w_o,
-                              layer.mha2.b_o, out1, layer.ln2)
-                ffn = layer.ffn
-                h = lin(out2, ffn.w1, ffn.b1, activation="relu")
-                x = lin_ln(h, ffn.w2, ffn.b2, out2, layer.ln3)
-            logits = lin(x, self.model.w_final, self.model.b_final)
+                return attn2.reshape(B, 1, H * dh)
+
+            if skinny_preln:
+                logits = _preln_layers(self.model, x, self_attn, cross_attn)
+            else:
+                for li, layer in enumerate(dec.layers):
+                    qkv = lin(x, layer.mha1.w_qkv, layer.mha1.b_qkv)
+                    out1 = lin_ln(self_attn(li, qkv), layer.mha1.w_o,
+                                  layer.mha1.b_o, x, layer.ln1)
+                    q2 = lin(out1, layer.mha2.w_q, layer.mha2.b_q)
+                    out2 = lin_ln(cross_attn(li, q2), layer.mha2.w_o,
+                                  layer.mha2.b_o, out1, layer.ln2)
+                    ffn = layer.ffn
+                    h = lin(out2, ffn.w1, ffn.b1, activation="relu")
+                    x = lin_ln(h, ffn.w2, ffn.b2, out2, layer.ln3)
+                logits = lin(x, self.model.w_final, self.model.b_final)
             nxt = O.argmax_lastdim(logits).view(B, 1)
             self.tok.index_copy_(1, pos + 1, nxt)
             self.pos.add_(1)

@@ -58,6 +58,7 @@ from .functional import (  # noqa: E402
     linear_rows,
     linear_rows_residual_layernorm,
     linear_rows_workspace,
+    residual_layernorm_linear,
     beam_search_workspace,
     beam_topk,
     beam_gather_table,

@@ -102,6 +102,10 @@ torch::Tensor linear_rows_ln(torch::Tensor x, torch::Tensor w,
                              torch::Tensor beta, double eps, torch::Tensor ws,
                              int64_t nw);
 torch::Tensor linear_rows_workspace(int64_t M, int64_t N);
+std::vector<torch::Tensor> linear_rows_preln(
+    torch::Tensor p, torch::Tensor res, torch::Tensor gamma,
+    torch::Tensor beta, double eps, torch::Tensor w,
+    c10::optional<torch::Tensor> bias, bool relu, int64_t nw);
 
 std::vector<torch::Tensor> beam_topk(torch::Tensor logits,
                                      torch::Tensor scores,
@@ -310,6 +314,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "zeroed ticket + fp32 (M,N) pre-norm rows for linear_rows_ln; "
         "allocate once outside graph capture, share per stream only",
         pybind11::arg("M"), pybind11::arg("N"));
+  m.def("linear_rows_preln", &linear_rows_preln,
+        "[xn, y]: xn = LayerNorm(p + res; gamma, beta, eps) (M,K), y = xn @ "
+        "W^T (+bias)(+ReLU) (M,N), in one launch; every block normalises the "
+        "rows itself, y is bit-equal to linear_rows(xn, ..).  1 <= M <= 64, "
+        "K % 8 == 0, K <= 1024, operands contiguous and 16-byte aligned.  "
+        "nw 0 = host rule, else 4",
+        pybind11::arg("p"), pybind11::arg("res"), pybind11::arg("gamma"),
+        pybind11::arg("beta"), pybind11::arg("eps"), pybind11::arg("w"),
+        pybind11::arg("bias") = pybind11::none(),
+        pybind11::arg("relu") = false, pybind11::arg("nw") = 0);
   m.def("beam_topk", &beam_topk,
         "beam-search candidate selection in one launch: per sentence the K "
         "best of K*V by scores[b,k] + log_softmax(logits[b,k])[v], ties to "

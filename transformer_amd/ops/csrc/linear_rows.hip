@@ -44,6 +44,19 @@
 // No block reads what another wrote before the gate.  The linear's output is
 // never rounded to bf16 on the way to the LayerNorm.
 //
+// Pre-LN variant (linear_rows_preln).  The LayerNorm of the linear's INPUT:
+// XN = LN(P + R), Y = act(XN . W^T + bias).  A LayerNorm row needs only its
+// own row and every block reads all of X anyway, so every block normalises
+// all M rows itself before its K loop: no ticket, no workspace, no tail, no
+// block reading what another block of the launch wrote.  A quarter-wave owns
+// a row (4 rows per wave, a 16-row group per pass of the 4 waves): 16-byte
+// loads of P and R, the fp32 sum kept in registers, mean then centred
+// squares reduced by 4 xor-shuffles, bf16 rows written to a padded LDS tile
+// (rows >= M as zeros), one barrier.  The K loop is the plain kernel's, with
+// the X fragments read from the tile, so Y is bit-equal to linear_rows(XN).
+// A wave's first W loads are issued before the prologue.  Row m of XN goes
+// to global from block m % gridDim.x, out of the registers that hold it.
+//
 // Workspace: [ticket: 1 word, padded to 4][t: M*N floats].  Calls on one
 // stream may share it (they are stream-ordered); calls on different streams
 // must NOT.
@@ -54,6 +67,8 @@
 
 #define LR_MAX_M 64
 #define LR_LN_MAX_N 2048     // LN tail keeps a row in registers
+#define LR_PRE_MAX_K 1024    // pre-LN prologue keeps a row in 16 lanes
+#define LR_PRE_PAD 8         // tile row stride K + 8: 16 rows, 16 banks apart
 
 typedef __bf16 bf16x8l __attribute__((ext_vector_type(8)));
 
@@ -122,7 +137,93 @@ DEV_INLINE void lr_ln_rows(const float* t, const short* __restrict__ gamma,
   }
 }
 
-// vec: N % 4 == 0 and bias/res/y/ws 8-(16-)byte aligned -> vector epilogue.
+// K steps a wave has in flight: 8 loads of W/X per lane and step at MG=4
+template <int MG> constexpr int lr_unr() { return MG == 4 ? 2 : 4; }
+
+// W fragments of steps s0, s0 + NW, ..: wp already carries row and k-group.
+template <int MG, int NW>
+DEV_INLINE void lr_load_w(s16x8 (&wv)[lr_unr<MG>()][2], const short* wp,
+                          bool wlive, int s0, int g, int K) {
+  const s16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+  for (int u = 0; u < lr_unr<MG>(); ++u)
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int k = (s0 + u * NW) * 64 + h * 8;
+      wv[u][h] = (k + g * 16 + 8 <= K && wlive) ? *(const s16x8*)(wp + k)
+                                                : zero8;
+    }
+}
+
+// Pre-LN prologue: tile[16*MG][K + LR_PRE_PAD] = bf16(LN(P + R)), rows >= M
+// zero; row m also to XN from block m % gridDim.x.  Lane j of a quarter-wave
+// holds the 16-byte chunks j, j + 16, .. of its row.
+template <int MG, int NW>
+DEV_INLINE void lr_preln_tile(const short* __restrict__ P,
+                              const short* __restrict__ R,
+                              const short* __restrict__ gamma,
+                              const short* __restrict__ beta,
+                              short* __restrict__ XN, short* tile, int M,
+                              int K, float eps, int wave, int lane) {
+  static_assert(NW == 4, "4 waves x 4 rows = one 16-row group per pass");
+  constexpr int NCH = LR_PRE_MAX_K / 128;
+  const s16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+  const int j = lane & 15, ld = K + LR_PRE_PAD;
+  const float inv_k = 1.0f / (float)K;
+#pragma unroll 1
+  for (int mg = 0; mg < MG; ++mg) {
+    const int m = mg * 16 + wave * 4 + (lane >> 4);
+    const bool live = m < M;
+    float t[NCH][8], s = 0.f;
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+      const int k = (j + 16 * i) * 8;
+      const bool in = live && k < K;
+      const s16x8 pv = in ? *(const s16x8*)(P + (long)m * K + k) : zero8;
+      const s16x8 rv = in ? *(const s16x8*)(R + (long)m * K + k) : zero8;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        t[i][e] = bfbits2f(pv[e]) + bfbits2f(rv[e]);
+        s += t[i][e];
+      }
+    }
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    const float mean = s * inv_k;
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+      const bool in = (j + 16 * i) * 8 < K;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float d = t[i][e] - mean;
+        q += in ? d * d : 0.f;
+      }
+    }
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) q += __shfl_xor(q, off);
+    const float rs = rsqrtf(q * inv_k + eps);
+    const bool mine = live && m % (int)gridDim.x == (int)blockIdx.x;
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+      const int k = (j + 16 * i) * 8;
+      if (k >= K) continue;
+      s16x8 ov = zero8;
+      if (live) {
+        const s16x8 gv = *(const s16x8*)(gamma + k);
+        const s16x8 bv = *(const s16x8*)(beta + k);
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          ov[e] = f2bfbits((t[i][e] - mean) * rs * bfbits2f(gv[e]) +
+                           bfbits2f(bv[e]));
+      }
+      *(s16x8*)(tile + m * ld + k) = ov;
+      if (mine) *(s16x8*)(XN + (long)m * K + k) = ov;
+    }
+  }
+  __syncthreads();
+}
+
 template <int MG, int NW, bool LN>
 __global__ __launch_bounds__(NW * WAVE)
 void linear_rows_kernel(const short* __restrict__ X,
@@ -132,108 +233,27 @@ void linear_rows_kernel(const short* __restrict__ X,
                         const short* __restrict__ res,
                         const short* __restrict__ gamma,
                         const short* __restrict__ beta, float* ws, float eps) {
-  // K steps a wave has in flight: 8 loads of W/X per lane and step at MG=4
-  constexpr int UNR = MG == 4 ? 2 : 4;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int g = lane >> 4, r16 = lane & 15;
-  const int n0 = blockIdx.x * 16;
-  const int nrow = n0 + r16;                  // this lane's W row
-  const bool wlive = nrow < N;
-  const short* wp = W + (long)nrow * K + g * 16;
-  const short* xp = X + (long)r16 * K + g * 16;
+  constexpr bool PRE = false;
+  short* const XN = nullptr;
+  short* const tile = nullptr;
+#include "linear_rows_body.inc"
+}
 
-  f32x4 acc[MG];
-#pragma unroll
-  for (int mg = 0; mg < MG; ++mg) acc[mg] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const s16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
-  const int nsteps = cdiv(K, 64);
-  for (int s0 = wave; s0 < nsteps; s0 += NW * UNR) {
-    s16x8 wv[UNR][2], xv[UNR][MG][2];
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        // steps past nsteps start at k >= K: the one test covers both
-        const int k = (s0 + u * NW) * 64 + h * 8;    // + g*16 in wp/xp
-        const bool kin = k + g * 16 + 8 <= K;
-        wv[u][h] = (kin && wlive) ? *(const s16x8*)(wp + k) : zero8;
-#pragma unroll
-        for (int mg = 0; mg < MG; ++mg)
-          xv[u][mg][h] = (kin && mg * 16 + r16 < M)
-                             ? *(const s16x8*)(xp + (long)mg * 16 * K + k)
-                             : zero8;
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < UNR; ++u)
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int mg = 0; mg < MG; ++mg)
-          acc[mg] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              (bf16x8l)wv[u][h], (bf16x8l)xv[u][mg][h], acc[mg], 0, 0, 0);
-  }
-
-  // waves -> block: wave mg sums group mg's partials in wave order
-  __shared__ __attribute__((aligned(16))) float s_part[NW][MG][WAVE][4];
-#pragma unroll
-  for (int mg = 0; mg < MG; ++mg) *(f32x4*)s_part[wave][mg][lane] = acc[mg];
-  __syncthreads();
-
-  if (wave < MG) {
-    const int mg = wave;
-    f32x4 v = *(const f32x4*)s_part[0][mg][lane];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) v += *(const f32x4*)s_part[w][mg][lane];
-    const int m = mg * 16 + r16, n = n0 + g * 4;
-    if (m < M && n < N) {
-      const long o = (long)m * N + n;
-      if (vec) {                               // n + 4 <= N: N % 4 == 0
-        if (bias != nullptr) {
-          const s16x4 bv = *(const s16x4*)(bias + n);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] += bfbits2f(bv[r]);
-        }
-        if constexpr (LN) {
-          const s16x4 rv = *(const s16x4*)(res + o);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] += bfbits2f(rv[r]);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) lr_ws_store(ws + 4 + o + r, v[r]);
-        } else {
-          s16x4 ov;
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            ov[r] = f2bfbits(relu ? fmaxf(v[r], 0.f) : v[r]);
-          *(s16x4*)(Y + o) = ov;
-        }
-      } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          if (n + r >= N) break;
-          float a = v[r];
-          if (bias != nullptr) a += bfbits2f(bias[n + r]);
-          if constexpr (LN) {
-            lr_ws_store(ws + 4 + o + r, a + bfbits2f(res[o + r]));
-          } else {
-            Y[o + r] = f2bfbits(relu ? fmaxf(a, 0.f) : a);
-          }
-        }
-      }
-    }
-  }
-
-  if constexpr (LN) {
-    // last_arriver drains each wave's write-through stores (vmcnt) before
-    // the ticket, and its winner takes an agent acquire before the loads
-    unsigned* ticket = (unsigned*)ws;
-    if (!last_arriver(ticket, gridDim.x)) return;
-    lr_ln_rows<NW>(ws + 4, gamma, beta, Y, M, N, eps, wave, lane);
-    if (tid == 0)
-      __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-  }
+// Dynamic LDS: the 16*MG x (K + LR_PRE_PAD) bf16 tile.
+template <int MG, int NW>
+__global__ __launch_bounds__(NW * WAVE)
+void linear_rows_preln_kernel(const short* __restrict__ X,
+                              const short* __restrict__ res,
+                              const short* __restrict__ gamma,
+                              const short* __restrict__ beta, float eps,
+                              const short* __restrict__ W,
+                              const short* __restrict__ bias,
+                              short* __restrict__ XN, short* __restrict__ Y,
+                              int M, int N, int K, int relu, int vec) {
+  constexpr bool LN = false, PRE = true;
+  float* const ws = nullptr;
+  extern __shared__ __attribute__((aligned(16))) short tile[];
+#include "linear_rows_body.inc"
 }
 
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -347,4 +367,65 @@ torch::Tensor linear_rows_ln(torch::Tensor x, torch::Tensor w,
   lr_launch<true>(x, w, bp, y, false, vec, (const short*)res.data_ptr(), gp,
                   btp, ws.data_ptr<float>(), (float)eps, nw);
   return y;
+}
+
+// One pre-LN instantiation: raises its dynamic-LDS limit to the largest
+// tile it serves the first time a device sees it, then launches.
+template <int MG>
+static void lr_preln_go(hipStream_t stream, int dev, const short* p,
+                        const short* r, const short* gamma, const short* beta,
+                        float eps, const short* w, const short* bias,
+                        short* xn, short* y, int M, int N, int K, bool relu,
+                        bool vec) {
+  auto kern = linear_rows_preln_kernel<MG, 4>;
+  static unsigned long long raised = 0;      // bit per device
+  if (!(raised >> dev & 1ull)) {
+    const int most = 16 * MG * (LR_PRE_MAX_K + LR_PRE_PAD) * 2;
+    C10_HIP_CHECK(hipFuncSetAttribute(
+        (const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, most));
+    raised |= 1ull << dev;
+  }
+  const size_t lds = (size_t)16 * MG * (K + LR_PRE_PAD) * 2;
+  kern<<<cdiv(N, 16), 4 * WAVE, lds, stream>>>(p, r, gamma, beta, eps, w, bias,
+                                              xn, y, M, N, K, relu ? 1 : 0,
+                                              vec ? 1 : 0);
+}
+
+std::vector<torch::Tensor> linear_rows_preln(
+    torch::Tensor p, torch::Tensor res, torch::Tensor gamma,
+    torch::Tensor beta, double eps, torch::Tensor w,
+    c10::optional<torch::Tensor> bias, bool relu, int64_t nw) {
+  lr_check_xw(p, w);
+  const int64_t M = p.size(0), K = p.size(1), N = w.size(0);
+  TORCH_CHECK(K <= LR_PRE_MAX_K, "linear_rows_preln: K <= ", LR_PRE_MAX_K);
+  TORCH_CHECK(nw == 0 || nw == 4,
+              "linear_rows_preln: nw must be 0 (rule) or 4");
+  TORCH_CHECK(lr_nw(K) == 4, "linear_rows_preln: 4 waves per block only");
+  TORCH_CHECK(res.is_cuda() && res.dtype() == torch::kBFloat16 &&
+              res.is_contiguous() && res.dim() == 2 && res.size(0) == M &&
+              res.size(1) == K && lr_al(res.data_ptr(), 16),
+              "linear_rows_preln: res must be a contiguous, 16-byte aligned "
+              "bf16 (M,K) tensor");
+  const short* bp = lr_vecN(bias, N, "bias");
+  const short* gp = lr_vecN(gamma, K, "gamma");
+  const short* btp = lr_vecN(beta, K, "beta");
+  TORCH_CHECK(gp != nullptr && btp != nullptr && lr_al(gp, 16) &&
+              lr_al(btp, 16),
+              "linear_rows_preln: gamma and beta are required, 16-byte "
+              "aligned");
+  auto xn = torch::empty({M, K}, p.options());
+  auto y = torch::empty({M, N}, p.options());
+  TORCH_CHECK(lr_al(xn.data_ptr(), 16), "linear_rows_preln: xn alignment");
+  const bool vec = N % 4 == 0 && lr_al(bp, 8) && lr_al(y.data_ptr(), 8);
+  const int dev = p.get_device();
+  TORCH_CHECK(dev >= 0 && dev < 64, "linear_rows_preln: device index");
+  auto stream = at::hip::getCurrentHIPStream();
+#define LRP_GO(MGC)                                                          \
+  lr_preln_go<MGC>(stream, dev, (const short*)p.data_ptr(),                  \
+                   (const short*)res.data_ptr(), gp, btp, (float)eps,        \
+                   (const short*)w.data_ptr(), bp, (short*)xn.data_ptr(),    \
+                   (short*)y.data_ptr(), (int)M, (int)N, (int)K, relu, vec)
+  if (M <= 16) LRP_GO(1); else if (M <= 32) LRP_GO(2); else LRP_GO(4);
+#undef LRP_GO
+  return {xn, y};
 }

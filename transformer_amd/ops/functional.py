@@ -763,6 +763,41 @@ def linear_rows_residual_layernorm(x, w, b, res, gamma, beta, eps, ws):
     return y.view(res.shape)
 
 
+def _preln_kernel_ok(p2, r2, gamma, beta, w, b):
+    """Where residual_layernorm_linear launches linear_rows_preln: linear_rows'
+    range with K <= 1024 and 16-byte aligned residual, gamma and beta, at
+    most 32 rows and at most 4096 output columns.  The fused launch measured
+    slower than ln_fwd + linear_rows at EVERY shape (docs/PERF.md, "LayerNorm
+    in the consuming decode linear"): by 0.5-0.9 us inside this range, which
+    the opt-in skinny_preln flag keeps reachable, and 1.5x-4.7x outside it
+    (64 rows: every block normalises 64 rows; the 32k head: 2001 blocks
+    repeat the prologue), where it is never launched."""
+    M, K = p2.shape
+    return (_rows_kernel_ok(p2, w, b) and K <= 1024 and M <= 32
+            and w.shape[0] <= 4096
+            and r2.dtype == torch.bfloat16 and r2.shape == p2.shape
+            and r2.data_ptr() % 16 == 0
+            and all(t is not None and _vec_ok(t, K) and t.data_ptr() % 16 == 0
+                    for t in (gamma, beta)))
+
+
+def residual_layernorm_linear(pre, res, gamma, beta, eps, w, b=None,
+                              activation=None):
+    """(xn, y): xn = LN(pre + res), y = xn @ W^T + b (+ReLU), the LayerNorm
+    folded into the prologue of the decode linear that consumes it: one
+    launch, y bit-equal to linear_rows(xn, ..).  Forward only.  CPU tensors
+    and whatever _preln_kernel_ok turns away get
+    residual_layernorm followed by linear_rows."""
+    p2 = pre.reshape(-1, pre.shape[-1]).contiguous()
+    r2 = res.reshape(-1, res.shape[-1]).contiguous()
+    if not _preln_kernel_ok(p2, r2, gamma, beta, w, b):
+        xn = residual_layernorm(pre, res, gamma, beta, eps)
+        return xn, linear_rows(xn, w, b, activation)
+    xn, y = ext().linear_rows_preln(p2, r2, gamma, beta, eps, w, b,
+                                    activation == "relu")
+    return xn.view(pre.shape), y.view(*pre.shape[:-1], w.shape[0])
+
+
 # ---------------------------------------------------------------------------
 # Beam search (forward only, csrc/beam_search.hip): candidate selection and
 # the self-attention cache reorder, one launch each per decode step.
