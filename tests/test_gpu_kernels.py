@@ -73,7 +73,7 @@ def test_gemm256_nt(m, n, k, epi):
     (16384, 512, 512),    # split-M accumulation path (128-tile)
     (4096, 1536, 512),    # 256-tile path
     (1000, 2049, 300),    # 256-tile path, ragged n/k/m edges
-    (200, 130, 70),       # ragged every dim, single-slice path
+    (200, 130, 70),       # ragged every dim; 4 slices, 8-row tail in the last
     (64, 512, 512),
 ])
 def test_gemm_dw(m, n, k):

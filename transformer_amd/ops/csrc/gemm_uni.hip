@@ -461,16 +461,20 @@ torch::Tensor gemm_uni_nt(torch::Tensor a, torch::Tensor w,
 
 // C[M,N] = A[M,K] @ B[K,N] — dX = dY @ W, NT x TR (W read red-major via
 // tr16, so the weight needs no transpose).  K = W's row count, %64 == 0.
+// W may be a [:, :N] view of a wider buffer (a ragged N padded out to the
+// tile, like gemm_uni_tn's operands); gemm_uni_launch checks its row stride
+// against the tile span.
 torch::Tensor gemm_uni_nn(torch::Tensor a, torch::Tensor w,
                           c10::optional<torch::Tensor> out) {
   TORCH_CHECK(a.is_cuda() && a.dtype() == torch::kBFloat16 && a.dim() == 2 &&
               a.stride(1) == 1, "gemm_uni_nn: bad a");
   TORCH_CHECK(w.is_cuda() && w.dtype() == torch::kBFloat16 && w.dim() == 2 &&
-              w.is_contiguous(), "gemm_uni_nn: bad w");
+              w.stride(1) == 1 && w.stride(0) >= w.size(1),
+              "gemm_uni_nn: bad w");
   const int M = a.size(0), K = a.size(1), N = w.size(1);
   TORCH_CHECK(w.size(0) == K, "gemm_uni_nn: K mismatch");
   return gemm_uni_launch(a, w, c10::nullopt, 0, out, M, N, K,
-                         a.stride(0), N, false, true, 1);
+                         a.stride(0), w.stride(0), false, true, 1);
 }
 
 // C[N,K] = A[M,N]^T @ B[M,K] — dW = dY^T @ X, TR x TR; contraction M%64==0.
